@@ -19,8 +19,17 @@ returns), so the timed window ends when the work does, not when the unluckiest
 client's K-th request does.
 K steps are timed between a barrier + torch.cuda.synchronize() on every
 rank; time = max over ranks; ``value`` = completed RPCs / that time.
-After timing, N>1 runs BASELINE config 5 through the service: one gang
-Execute with gpus=N whose ranks all-reduce over RCCL/xGMI.
+A plain run does only that: set up, warm up, time the K steps, print the
+headline line.  ``--dump-outputs DIR`` also writes what the last timed
+step's Executes returned (the numbers the payload printed) as DIR/<name>.npy;
+the payload's draws are seeded (``--seed``), so the same arguments give the
+same inputs and two builds can be compared output for output.
+
+``--full`` adds everything else to the line: the idle-CPU profile, CPU and
+GPU time per Execute by role, the materialised-draw run, executor, admission
+and memory figures, what bounds the node, and for N>1 BASELINE config 5
+through the service: one gang Execute with gpus=N whose ranks all-reduce
+over RCCL/xGMI.
 """
 
 from __future__ import annotations
@@ -131,7 +140,8 @@ def parse_args():
                         "(no kernel broker, no HIP warm-up); use with a CPU workload such as --workload hello")
     p.add_argument("--no-gang-check", action="store_true")
     p.add_argument("--idle-probe", type=float, default=2.0,
-                   help="seconds of CPU sampling with the service idle (after READY, before the clients); 0 = skip")
+                   help="seconds the service sits idle after READY, before the clients (with --full its CPU is sampled "
+                        "meanwhile); 0 = skip")
     p.add_argument("--fold", action="store_true",
                    help="keep one executor daemon (broker, HIP context, pools) per requested GPU even when fewer GPUs "
                         "are visible: the N-GPU node's topology rehearsed on this box")
@@ -141,8 +151,81 @@ def parse_args():
                    help="Execute with numpy_offload=True: numpy.random draws of the payload live on the sandbox's GPU "
                         "and numpy calls on them run on the beekern kernels (ops/numpy_offload.py)")
     p.add_argument("--materialized-steps", type=int, default=-1,
-                   help="steps of the secondary materialised-draw run (numpy's HBM traffic; -1 = min(steps, 20), 0 = skip)")
+                   help="with --full: steps of the secondary materialised-draw run (numpy's HBM traffic; "
+                        "-1 = min(steps, 20), 0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline figure: the idle-CPU profile, CPU / GPU time per Execute by role, "
+                        "the materialised-draw run, the gang all-reduce check (N > 1), admission checks, executor and "
+                        "memory statistics, what bounds the node.  Without it a run sets up, warms up, times the steps "
+                        "and prints the headline line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step's Executes returned (every number a "
+                        "payload printed, and the exit codes) as DIR/<name>.npy, float64")
+    p.add_argument("--seed", type=int, default=20240611,
+                   help="seed of the payload's random draws (beekern / numpy.random): the same arguments give the same "
+                        "inputs, so two builds can be compared output for output")
     return p.parse_args()
+
+
+_SEED_PROLOGUE = (
+    # (module the payload imports, the line that seeds its global generator)
+    ("beekern", "import beekern as _bee_seed; _bee_seed.random.seed({seed}); del _bee_seed\n"),
+    ("numpy", "import numpy as _bee_seed; _bee_seed.random.seed({seed}); del _bee_seed\n"),
+)
+
+
+def seeded(source: str, seed: int) -> str:
+    """The payload with its random generators seeded: one line in front per
+    generator module the payload itself imports (none is added that it does
+    not import, so it is routed to the same sandbox kind).  Every Execute of a
+    run sends the same text -- the service's per-source caches (routing,
+    precompiled payload) work as for any re-submitted script -- and so draws
+    the same inputs."""
+    import re
+
+    lines = [line.format(seed=seed) for mod, line in _SEED_PROLOGUE
+             if re.search(rf"^\s*(?:import|from)\s+{mod}\b", source, re.M)]
+    return "".join(lines) + source
+
+
+_NUMBER_LINE = None
+
+
+def printed_numbers(stdout: str) -> dict:
+    """{label: value} of a payload's ``Label: number`` lines -- what a caller
+    of Execute gets back -- without its own wall-clock line."""
+    global _NUMBER_LINE
+    if _NUMBER_LINE is None:
+        import re
+
+        _NUMBER_LINE = re.compile(r"^([A-Za-z][\w ]*?):[ \t]*(\S+)", re.M)
+    out = {}
+    for label, value in _NUMBER_LINE.findall(stdout):
+        if label == "Execution Time" or label in out:
+            continue
+        try:
+            out[label] = float(value)
+        except ValueError:
+            pass
+    return out
+
+
+def dump_outputs(directory: str, last_step) -> list:
+    """``last_step``: (load generator, request index, exit code, stdout) of
+    the last timed step's Executes.  One float64 array per printed label (in
+    load-generator, then request order; NaN where an Execute did not print
+    it) and ``exit_code``; returns the file names."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    rows = [(rc, printed_numbers(text)) for _, _, rc, text in sorted(last_step, key=lambda r: (r[0], r[1]))]
+    arrays = {"exit_code": [float(rc) for rc, _ in rows]}
+    for label in sorted({k for _, nums in rows for k in nums}):
+        name = "_".join(label.lower().split())
+        arrays[name] = [nums.get(label, float("nan")) for _, nums in rows]
+    for name, values in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(values, dtype=np.float64))
+    return sorted(name + ".npy" for name in arrays)
 
 
 def dist_env():
@@ -528,9 +611,10 @@ async def close_clients(chans):
 
 
 async def client_loop(stub, pb, source, budget, out, trace=None, extra=None):
-    lat, errors, exec_times, phases, checks = out
+    lat, errors, exec_times, phases, checks, last = out
     while budget[0] > 0:
         budget[0] -= 1  # (one event loop: taken before the await, no race)
+        index = budget[1] - budget[0] - 1  # of this request among the run's
         t = time.perf_counter()
         try:
             r = await stub.Execute(pb.ExecuteRequest(source_code=source, **(extra or {})), timeout=600)
@@ -539,6 +623,8 @@ async def client_loop(stub, pb, source, budget, out, trace=None, extra=None):
             continue
         t1 = time.perf_counter()
         lat.append((t1 - t) * 1e3)
+        if index >= budget[2]:  # the last step's: what --dump-outputs writes
+            last.append((index, r.exit_code, r.stdout))
         if trace is not None:
             trace.append((round(t1, 6), round((t1 - t) * 1e3, 3)))
         for k, v in r.timings_ms.items():
@@ -570,8 +656,8 @@ async def run_clients(stubs, source, n, trace=None, extra=None):
     the offered concurrency."""
     from bee_code_interpreter_fs_amd.models import proto as pb
 
-    out = ([], [], [], {}, {"result_ok": 0, "gemm_ok": 0})
-    budget = [n * len(stubs)]
+    out = ([], [], [], {}, {"result_ok": 0, "gemm_ok": 0}, [])
+    budget = [n * len(stubs), n * len(stubs), (n - 1) * len(stubs)]  # left, all, first of the last step
     await asyncio.gather(*(client_loop(stub, pb, source, budget, out, trace, extra) for stub in stubs))
     return out
 
@@ -595,14 +681,13 @@ def _loadgen_main(targets, first, source, concurrency, warmup, steps, barrier, r
         if go is not None:
             go.wait()
         t0 = time.perf_counter()
-        lat, errors, exec_times, phases, checks = loop.run_until_complete(run_clients(stubs, source, steps,
-                                                                                     extra=extra))
-        results.put((time.perf_counter() - t0, lat, errors, exec_times, phases, checks))
+        out = loop.run_until_complete(run_clients(stubs, source, steps, extra=extra))
+        results.put((time.perf_counter() - t0,) + tuple(out))
     except BaseException as e:  # noqa: BLE001 - report instead of hanging the barrier
         barrier.abort()
         if go is not None:
             go.abort()
-        results.put((0.0, [], [f"loadgen failed: {e!r}"[:300]], [], {}, {}))
+        results.put((0.0, [], [f"loadgen failed: {e!r}"[:300]], [], {}, {}, []))
     finally:
         if chans:
             loop.run_until_complete(close_clients(chans))
@@ -916,7 +1001,8 @@ def main():
             torch.cuda.synchronize()
 
     script, metric, model, dtype = WORKLOADS[args.workload]
-    source = open(args.payload or os.path.join(ROOT, script)).read()
+    source = seeded(open(args.payload or os.path.join(ROOT, script)).read(), args.seed)
+    full = args.full
     extra = {"numpy_offload": True} if args.numpy_offload else None
     if args.numpy_offload:
         metric = metric.replace("numpy on CPU", "numpy offloaded to the GPU (numpy_offload)")
@@ -958,13 +1044,24 @@ def main():
         idle = None
         if rank == 0:
             wait_pools_ready(hport)
-            if args.idle_probe > 0:
+            if args.idle_probe > 0 and full:
                 idle = idle_profile(proc.pid, args.idle_probe)
+            elif args.idle_probe > 0:
+                # the same pause without the sampling: it lets the self-warm's
+                # sandbox teardown and the pool refill finish before a short
+                # timed window (profiles/archive/r4_idle_probe_ab.jsonl), so
+                # the headline figure needs it
+                time.sleep(args.idle_probe)
         if world > 1:
             dist.barrier()
         cpu0, cpu_src = cpu_usage_s()
         svc_pid = proc.pid if proc is not None else None
-        if loadgens > 1:
+        cpu_busy, thr0, thr1 = 0.0, {}, {}
+        roles0 = roles1 = slots0 = slots1 = threads0 = threads1 = None
+        if loadgens > 1 and not full:
+            gathered = gather_ranks(run_loadgens(loadgens, targets, source, per_lg, args.warmup, args.steps, barrier,
+                                                 first=first, extra=extra))
+        elif loadgens > 1:
             marks = {"roles0": None, "svc": svc_pid, "hport": hport if rank == 0 else None}
             gathered = gather_ranks(run_loadgens(loadgens, targets, source, per_lg, args.warmup, args.steps, barrier,
                                                  marks, first=first, extra=extra))
@@ -981,41 +1078,43 @@ def main():
                 gc.collect()
                 gc.freeze()  # the clients' heap out of the timed window's collections
             barrier()
-            thr0 = cpu_throttle()
-            roles0 = cpu_by_role(svc_pid)
-            threads0 = daemon_threads(svc_pid)
-            slots0 = slot_executions(hport) if rank == 0 else None
+            if full:
+                thr0 = cpu_throttle()
+                roles0 = cpu_by_role(svc_pid)
+                threads0 = daemon_threads(svc_pid)
+                slots0 = slot_executions(hport) if rank == 0 else None
             trace = [] if os.environ.get("BEE_BENCH_TRACE") else None
             # the container's CPU counter right around the timed window: the
             # samplers above and below (/proc walks, a status call through the
             # front-end) stay out of CPU per Execute
             cpu0, cpu_src = cpu_usage_s()
             t0 = time.perf_counter()
-            lat, errors, exec_times, phases, checks = loop.run_until_complete(
+            lat, errors, exec_times, phases, checks, last = loop.run_until_complete(
                 run_clients(stubs, source, args.steps, trace, extra=extra))
             barrier()
             elapsed = time.perf_counter() - t0
             cpu1 = cpu_usage_s()[0]
-            thr1 = cpu_throttle()
-            roles1 = cpu_by_role(svc_pid)
-            threads1 = daemon_threads(svc_pid)
-            slots1 = slot_executions(hport) if rank == 0 else None
+            if full:
+                thr1 = cpu_throttle()
+                roles1 = cpu_by_role(svc_pid)
+                threads1 = daemon_threads(svc_pid)
+                slots1 = slot_executions(hport) if rank == 0 else None
             cpu_busy = (cpu1 - cpu0) / elapsed if elapsed > 0 else 0.0
-            gathered = [(elapsed, lat, errors, exec_times, phases, checks)]
+            gathered = [(elapsed, lat, errors, exec_times, phases, checks, last)]
             if trace is not None:  # completion time (s after t0) and latency of every timed Execute
                 with open(os.environ["BEE_BENCH_TRACE"], "w") as fh:
                     json.dump([(round(t - t0, 6), l) for t, l in trace], fh)
             if world > 1:
                 gathered = [None] * world
-                dist.all_gather_object(gathered, (elapsed, lat, errors, exec_times, phases, checks))
+                dist.all_gather_object(gathered, (elapsed, lat, errors, exec_times, phases, checks, last))
 
         # secondary: the same payload with every draw materialised in HBM
         # (the reference's numpy data movement), same clients, untimed by
         # the headline
         mat = None
         mat_steps = args.materialized_steps if args.materialized_steps >= 0 else min(args.steps, 20)
-        if args.workload == "numpy_gpu" and mat_steps > 0 and not args.payload:
-            msrc = open(MATERIALIZED).read()
+        if full and args.workload == "numpy_gpu" and mat_steps > 0 and not args.payload:
+            msrc = seeded(open(MATERIALIZED).read(), args.seed)
             if loadgens > 1:
                 mg = gather_ranks(run_loadgens(loadgens, targets, msrc, per_lg, 1, mat_steps, barrier, first=first))
             else:
@@ -1048,12 +1147,15 @@ def main():
             for g in gathered:
                 for k, v in g[4].items():
                     all_phases.setdefault(k, []).extend(v)
+            dumped = None
+            if args.dump_outputs:
+                dumped = dump_outputs(args.dump_outputs, [(i,) + tuple(r) for i, g in enumerate(gathered) for r in g[6]])
             ids = gpu_ids(n_gpus, args)
             # (a gang needs n distinct GPUs: RCCL refuses two ranks on one
             # device, so a folded rehearsal skips it)
             gang = (
                 gang_allreduce_check(target, n_gpus, hport=hport, virtual=args.virtual_gpus)
-                if n_gpus > 1 and not args.no_gang_check and not args.cpu_only and len(set(ids)) >= n_gpus
+                if full and n_gpus > 1 and not args.no_gang_check and not args.cpu_only and len(set(ids)) >= n_gpus
                 else None
             )
             total = len(all_lat)
@@ -1106,72 +1208,76 @@ def main():
             n_gemm = sum(g[5].get("gemm_ok", 0) for g in gathered)
             out["checked"] = {"result_ok": n_res, "gemm_rows_ok": n_gemm, "of": total}
             out["gemm_verified"] = total > 0 and n_gemm == total
-            if mat is not None:
-                out["materialized"] = mat
-            if gang is not None:
-                out["gang_allreduce"] = gang
-            out["executors"] = executor_stats(hport)
-            if not args.cpu_only:
-                out["admission_checks"] = admission_checks(target, len(gpu_ids(n_gpus, args)))
-            out["cpu_cores_busy"] = {"value": round(cpu_busy, 2), "source": cpu_src}
-            if roles0 is not None and roles1 is not None and total:
-                # CPU per Execute by role over the timed region (rank 0's node)
-                per = {k: round((roles1[k] - roles0[k]) * 1e3 / total, 3) for k in roles0}
-                per["all_cgroup"] = round(cpu_busy * max_elapsed * 1e3 / total, 3)
-                per["unattributed"] = round(per["all_cgroup"] - sum(v for k, v in per.items() if k != "all_cgroup"), 3)
-                out["cpu_ms_per_exec"] = per
-                if threads0 and threads1:
-                    th = {k: round((threads1.get(k, 0.0) - v) * 1e3 / total, 3) for k, v in threads0.items()}
-                    out["daemon_threads_ms_per_exec"] = dict(sorted(((k, v) for k, v in th.items() if v > 0.0005),
-                                                                    key=lambda kv: -kv[1]))
             out["ready_s"] = round(ready_s, 2)
-            if idle is not None:
-                out["idle_cpu"] = idle
-            # what bounds this node: the CPU quota over CPU per Execute is the
-            # rate the service could reach with the GPUs idle; a run near it is
-            # CPU-bound (more GPUs would not help), one well below it is set by
-            # latency / GPU time at the offered concurrency
-            quota, quota_src = cpu_quota_cores()
-            bound = {"cpu_quota_cores": round(quota, 2), "quota_source": quota_src,
-                     "cpu_utilisation_of_quota": round(cpu_busy / quota, 3) if quota else None}
-            # quota enforcement during the timed window: periods in which the
-            # container ran out of quota stall every process of it until the
-            # next period (latency the GPU never sees)
-            thr = throttle_delta(thr0, thr1)
-            if thr is not None:
-                bound["cpu_throttling"] = thr
-            if "cpu_ms_per_exec" in out and out["cpu_ms_per_exec"]["all_cgroup"] > 0:
-                cap = quota * 1e3 / out["cpu_ms_per_exec"]["all_cgroup"]
-                bound["cpu_bound_rps"] = round(cap, 1)
-                # the same without the load generators (they share this box's
-                # quota here; production clients run elsewhere)
-                svc_ms = out["cpu_ms_per_exec"]["all_cgroup"] - out["cpu_ms_per_exec"].get("bench_clients", 0.0)
-                if svc_ms > 0:
-                    bound["cpu_bound_rps_service_only"] = round(quota * 1e3 / svc_ms, 1)
-                bound["fraction_of_cpu_bound"] = round(out["value"] / cap, 3)
-                bound["bound_by"] = "cpu" if out["value"] >= 0.85 * cap or cpu_busy >= 0.9 * quota else \
-                    "latency/gpu at this concurrency"
-            gt = gpu_time_of(slots0, slots1, total, max_elapsed) if rank == 0 else None
-            if gt is not None:
-                out["gpu_time"] = gt
-                if gt.get("gpu_bound_rps"):
-                    bound["gpu_bound_rps"] = gt["gpu_bound_rps"]
-                    bound["gpu_utilisation"] = gt["gpu_utilisation"]
-                    if "cpu_bound_rps" in bound and gt["gpu_bound_rps"] < bound["cpu_bound_rps"]:
-                        bound["bound_by"] = "gpu" if out["value"] >= 0.85 * gt["gpu_bound_rps"] else bound["bound_by"]
-            out["node_bound"] = bound
-            # next to the measured value: the rate this node's CPU quota allows
-            # at the measured CPU per Execute -- a flat 1 -> N curve explains
-            # itself when value sits at it
-            out["cpu_bound_rps"] = bound.get("cpu_bound_rps")
-            out["gpu_bound_rps"] = bound.get("gpu_bound_rps")
-            out["pss_mb"] = pss_by_role(svc_pid)
-            if slots0 and slots1 and len(slots0) == len(slots1):
-                per_slot = [b - a for a, b in zip(slots0, slots1)]
-                mean = sum(per_slot) / len(per_slot)
-                out["slot_balance"] = {"executions": per_slot,
-                                       "max_dev_from_mean": round(max(abs(x - mean) for x in per_slot) / mean, 3)
-                                       if mean else None}
+            if dumped is not None:
+                out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped, "seed": args.seed}
+            if full:
+                if mat is not None:
+                    out["materialized"] = mat
+                if gang is not None:
+                    out["gang_allreduce"] = gang
+                out["executors"] = executor_stats(hport)
+                if not args.cpu_only:
+                    out["admission_checks"] = admission_checks(target, len(gpu_ids(n_gpus, args)))
+                out["cpu_cores_busy"] = {"value": round(cpu_busy, 2), "source": cpu_src}
+                if roles0 is not None and roles1 is not None and total:
+                    # CPU per Execute by role over the timed region (rank 0's node)
+                    per = {k: round((roles1[k] - roles0[k]) * 1e3 / total, 3) for k in roles0}
+                    per["all_cgroup"] = round(cpu_busy * max_elapsed * 1e3 / total, 3)
+                    per["unattributed"] = round(
+                        per["all_cgroup"] - sum(v for k, v in per.items() if k != "all_cgroup"), 3)
+                    out["cpu_ms_per_exec"] = per
+                    if threads0 and threads1:
+                        th = {k: round((threads1.get(k, 0.0) - v) * 1e3 / total, 3) for k, v in threads0.items()}
+                        out["daemon_threads_ms_per_exec"] = dict(sorted(((k, v) for k, v in th.items() if v > 0.0005),
+                                                                        key=lambda kv: -kv[1]))
+                if idle is not None:
+                    out["idle_cpu"] = idle
+                # what bounds this node: the CPU quota over CPU per Execute is the
+                # rate the service could reach with the GPUs idle; a run near it is
+                # CPU-bound (more GPUs would not help), one well below it is set by
+                # latency / GPU time at the offered concurrency
+                quota, quota_src = cpu_quota_cores()
+                bound = {"cpu_quota_cores": round(quota, 2), "quota_source": quota_src,
+                         "cpu_utilisation_of_quota": round(cpu_busy / quota, 3) if quota else None}
+                # quota enforcement during the timed window: periods in which the
+                # container ran out of quota stall every process of it until the
+                # next period (latency the GPU never sees)
+                thr = throttle_delta(thr0, thr1)
+                if thr is not None:
+                    bound["cpu_throttling"] = thr
+                if "cpu_ms_per_exec" in out and out["cpu_ms_per_exec"]["all_cgroup"] > 0:
+                    cap = quota * 1e3 / out["cpu_ms_per_exec"]["all_cgroup"]
+                    bound["cpu_bound_rps"] = round(cap, 1)
+                    # the same without the load generators (they share this box's
+                    # quota here; production clients run elsewhere)
+                    svc_ms = out["cpu_ms_per_exec"]["all_cgroup"] - out["cpu_ms_per_exec"].get("bench_clients", 0.0)
+                    if svc_ms > 0:
+                        bound["cpu_bound_rps_service_only"] = round(quota * 1e3 / svc_ms, 1)
+                    bound["fraction_of_cpu_bound"] = round(out["value"] / cap, 3)
+                    bound["bound_by"] = "cpu" if out["value"] >= 0.85 * cap or cpu_busy >= 0.9 * quota else \
+                        "latency/gpu at this concurrency"
+                gt = gpu_time_of(slots0, slots1, total, max_elapsed) if rank == 0 else None
+                if gt is not None:
+                    out["gpu_time"] = gt
+                    if gt.get("gpu_bound_rps"):
+                        bound["gpu_bound_rps"] = gt["gpu_bound_rps"]
+                        bound["gpu_utilisation"] = gt["gpu_utilisation"]
+                        if "cpu_bound_rps" in bound and gt["gpu_bound_rps"] < bound["cpu_bound_rps"]:
+                            bound["bound_by"] = "gpu" if out["value"] >= 0.85 * gt["gpu_bound_rps"] else bound["bound_by"]
+                out["node_bound"] = bound
+                # next to the measured value: the rate this node's CPU quota allows
+                # at the measured CPU per Execute -- a flat 1 -> N curve explains
+                # itself when value sits at it
+                out["cpu_bound_rps"] = bound.get("cpu_bound_rps")
+                out["gpu_bound_rps"] = bound.get("gpu_bound_rps")
+                out["pss_mb"] = pss_by_role(svc_pid)
+                if slots0 and slots1 and len(slots0) == len(slots1):
+                    per_slot = [b - a for a, b in zip(slots0, slots1)]
+                    mean = sum(per_slot) / len(per_slot)
+                    out["slot_balance"] = {"executions": per_slot,
+                                           "max_dev_from_mean": round(max(abs(x - mean) for x in per_slot) / mean, 3)
+                                           if mean else None}
             print(json.dumps(out), flush=True)
         if world > 1:
             dist.barrier()

@@ -146,7 +146,7 @@ def test_eight_gpu_rehearsal_balances_and_holds_the_bounds(tmp_path):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--virtual-gpus",
                         "--workload", "hello", "--steps", "25", "--warmup", "3", "--no-gang-check",
-                        "--max-inflight", "4"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--max-inflight", "4", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([line for line in p.stdout.splitlines() if line.startswith("{")][-1])
     assert out["errors"] == 0 and out["completed"] == 8 * 8 * 25, out

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_single_process_multi_gpu_run_scales_offered_load():
     p = subprocess.run(
         [sys.executable, "bench.py", "--gpus", "2", "--virtual-gpus", "--workload", "hello", "--steps", "4",
-         "--warmup", "1", "--concurrency", "3", "--no-gang-check"],
+         "--warmup", "1", "--concurrency", "3", "--no-gang-check", "--full"],
         cwd=ROOT, capture_output=True, text=True, timeout=600,
     )
     assert p.returncode == 0, p.stderr[-3000:]
@@ -56,6 +56,62 @@ def test_torchrun_two_ranks_one_json_line():
     assert out["n_gpus"] == 2 and out["errors"] == 0 and out["completed"] == 2 * 3 * 4, out
     assert out["steps"] == 4 and out["warmup"] == 1 and out["scaling"] == "weak"
     assert abs(out["value"] - out["completed"] / (out["ms_per_step"] * out["steps"] / 1e3)) < 0.05 * out["value"]
+
+
+FULL_ONLY_KEYS = {"executors", "admission_checks", "cpu_cores_busy", "cpu_ms_per_exec", "node_bound", "pss_mb",
+                  "idle_cpu", "materialized", "gang_allreduce", "slot_balance", "gpu_time"}
+
+
+def test_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the line carries the headline and what the responses
+    themselves say, nothing that takes sampling or runs of its own; and
+    --dump-outputs writes the last timed step's printed numbers, the same
+    from run to run because the payload's draws are seeded."""
+    import numpy as np
+
+    payload = tmp_path / "draw.py"
+    payload.write_text("import numpy as np\nx = np.random.rand(1000)\nprint('Sum of squares:', float((x * x).sum()))\n"
+                       "print('Mean:', float(x.mean()))\nprint('Execution Time:', 0.1, 'seconds')\n")
+    outs = []
+    for name in ("a", "b"):
+        p = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--virtual-gpus", "--workload", "numpy_cpu", "--payload",
+             str(payload), "--steps", "3", "--warmup", "1", "--concurrency", "2", "--idle-probe", "0",
+             "--dump-outputs", str(tmp_path / name)],
+            cwd=ROOT, capture_output=True, text=True, timeout=600,
+        )
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = json.loads([line for line in p.stdout.splitlines() if line.startswith("{")][-1])
+        assert out["steps"] == 3 and out["completed"] == 3 * 2 and out["errors"] == 0, out
+        assert abs(out["value"] - out["completed"] / (out["ms_per_step"] * out["steps"] / 1e3)) < 0.05 * out["value"]
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(out)
+        assert not (FULL_ONLY_KEYS & set(out)), FULL_ONLY_KEYS & set(out)
+        assert out["dumped_outputs"]["files"] == ["exit_code.npy", "mean.npy", "sum_of_squares.npy"], out["dumped_outputs"]
+        outs.append({f: np.load(tmp_path / name / f) for f in out["dumped_outputs"]["files"]})
+    for arrays in outs:
+        for f, a in arrays.items():
+            assert a.dtype == np.float64 and a.shape == (2,), (f, a)  # one value per Execute of the last step
+        assert (arrays["exit_code.npy"] == 0).all()
+        # 1000 draws of U[0, 1): sum of squares 333 +- 9.4 (sigma), mean 0.5 +- 0.009
+        assert abs(arrays["sum_of_squares.npy"][0] - 1000 / 3) < 60 and abs(arrays["mean.npy"][0] - 0.5) < 0.06
+    for f in outs[0]:
+        assert np.array_equal(outs[0][f], outs[1][f]), (f, outs[0][f], outs[1][f])
+
+
+def test_seed_prologue_and_output_parsing():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    src = "import time\n\nimport beekern as bk\nprint(bk.sum(bk.random.rand(8)))\n"
+    s = bench.seeded(src, 7)
+    assert s.endswith(src) and s.count("\n") == src.count("\n") + 1 and "random.seed(7)" in s and "numpy" not in s
+    assert bench.seeded("print('hello')\n", 7) == "print('hello')\n"  # nothing to seed: the payload as it is
+    both = bench.seeded("import numpy as np\nfrom beekern import random\n", 3)
+    assert both.count("random.seed(3)") == 2
+    compile(both, "<payload>", "exec")
+    nums = bench.printed_numbers("Result: 33331234.5\nGEMM checksum: -1.5e3\nGEMM max row error: 2.0\n"
+                                 "Execution Time: 0.002 seconds\nnote: fine\nplain line\n")
+    assert nums == {"Result": 33331234.5, "GEMM checksum": -1500.0, "GEMM max row error": 2.0}
 
 
 def _bf16(x):
@@ -192,7 +248,7 @@ def test_multi_gpu_bench_path_end_to_end_with_the_gang_check(n):
     env["BEE_BENCH_GANG_BUDGET_S"] = "200"
     p = subprocess.run(
         [sys.executable, "bench.py", "--gpus", str(n), "--virtual-gpus", "--workload", "hello", "--steps", "3",
-         "--warmup", "1", "--concurrency", "2", "--idle-probe", "0"],
+         "--warmup", "1", "--concurrency", "2", "--idle-probe", "0", "--full"],
         cwd=ROOT, env=env, capture_output=True, text=True, timeout=900,
     )
     assert p.returncode == 0, p.stderr[-3000:]

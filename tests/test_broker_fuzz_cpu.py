@@ -249,7 +249,7 @@ def _finish(p):
     return dict(kv.split("=") for kv in line.split()[1:])
 
 
-def test_client_batches_launches_into_one_send(fuzz_bin, tmp_path):
+def test_client_batches_launches_into_one_send(fuzz_bin, tmp_path, monkeypatch):
     """BrokerDriver queues fire-and-forget frames and sends them with the
     next request that wants a reply: the daemon's reader takes a batch in
     one read, replies (header + body) arrive in one message, and the
@@ -258,7 +258,8 @@ def test_client_batches_launches_into_one_send(fuzz_bin, tmp_path):
 
     from bee_code_interpreter_fs_amd.ops.driver import BeekernError, BrokerDriver
 
-    path = str(tmp_path / "b.sock")
+    monkeypatch.chdir(tmp_path)  # the socket by a relative name: sun_path holds 108 bytes, tmp_path may be longer
+    path = "b.sock"
     p = _serve(fuzz_bin, path)
     d = BrokerDriver(path)
     d.init(0)
@@ -288,10 +289,11 @@ def test_client_batches_launches_into_one_send(fuzz_bin, tmp_path):
     assert stats["live"] == "0"
 
 
-def test_client_queue_flushes_at_64_frames(fuzz_bin, tmp_path):
+def test_client_queue_flushes_at_64_frames(fuzz_bin, tmp_path, monkeypatch):
     from bee_code_interpreter_fs_amd.ops.driver import BrokerDriver
 
-    path = str(tmp_path / "b.sock")
+    monkeypatch.chdir(tmp_path)  # the socket by a relative name: sun_path holds 108 bytes, tmp_path may be longer
+    path = "b.sock"
     p = _serve(fuzz_bin, path)
     d = BrokerDriver(path)
     d.init(0)

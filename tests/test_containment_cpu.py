@@ -19,6 +19,8 @@ from __future__ import annotations
 
 import os
 import statistics
+import subprocess
+import sys
 import threading
 import time
 
@@ -79,19 +81,60 @@ def test_status_reports_containment(svc):
     assert con["mechanism"] == "procmon"
 
 
+_TOUCH = """
+import mmap, sys
+m = mmap.mmap(-1, int(sys.argv[1]), flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS)
+m.madvise(mmap.MADV_HUGEPAGE)  # (given back as whole huge pages, for the sandbox's huge pages)
+for off in range(0, len(m), mmap.PAGESIZE):
+    m[off] = 1
+"""
+
+
+def _back_host_memory(nbytes: int) -> None:
+    """Touch ``nbytes`` of this machine's memory once, on all its CPUs, and
+    give it back.  A virtual machine's memory is backed by its host only when
+    first written, and that first write costs the writer CPU time: 1.1 s per
+    GiB where this was measured against 0.3 s per GiB for memory touched
+    before (the same sandbox run twice in a row: 18.9 s, then 5.8 s), and
+    four times as much on a freshly started machine.  The sandbox below fills
+    16 GiB on the one core of ``limits.cpu``, so on fresh memory its 50 s went
+    to the hypervisor (kills at 62 s and 80 s, 16405 and 16496 MiB held) and
+    not to the monitor under test.  Nothing about the sandbox, its limits or
+    what is asserted of it changes."""
+    n = min(8, len(os.sched_getaffinity(0)))
+    procs = [subprocess.Popen([sys.executable, "-S", "-c", _TOUCH, str(nbytes // n)]) for _ in range(n)]
+    for p in procs:
+        p.wait(timeout=300)
+
+
 def test_memory_budget_covers_the_whole_tree(svc):
     """20 children of 3 GB each -- every one escaped its parent (setsid +
     double fork), as a daemonised helper would -- against a 16 GiB budget:
     the sandbox is killed as a whole once the tree holds more than that."""
+    _back_host_memory(18 * 1024**3)
     t0 = time.time()
     r = run(svc, """
-        import os, time
+        import fcntl, mmap, os, time
         print(os.getpid(), flush=True)
+        turn = os.path.join(os.environ.get("TMPDIR", "/tmp"), "turn")
         for i in range(20):
             if os.fork() == 0:
                 os.setsid()
                 if os.fork() == 0:
-                    b = bytearray(b"\\x01") * (3 * 1024**3)  # every page written
+                    # every page written -- one child at a time, in huge pages
+                    # where the kernel hands them out: 20 processes taking
+                    # 4 KiB faults at once spend the tree's one core contending
+                    # in the page allocator (1.37 against 0.69 s of CPU per GiB
+                    # with 8 of them on 8 CPUs; on memory touched before, the
+                    # budget was crossed after 19 s that way and after 5.8 s
+                    # this way)
+                    fd = os.open(turn, os.O_CREAT | os.O_RDWR, 0o600)
+                    fcntl.flock(fd, fcntl.LOCK_EX)
+                    b = mmap.mmap(-1, 3 * 1024**3, flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS)
+                    b.madvise(mmap.MADV_HUGEPAGE)
+                    for off in range(0, len(b), mmap.PAGESIZE):
+                        b[off] = 1
+                    os.close(fd)
                     time.sleep(120)
                 os._exit(0)
         time.sleep(60)

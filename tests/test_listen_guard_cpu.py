@@ -84,10 +84,11 @@ def test_own_clients_reach_own_servers(svc):
             server.close()
         asyncio.run(main())
 
-        # a Unix-domain server in the sandbox's own /tmp
-        path = os.path.join(os.environ.get("TMPDIR", "/tmp"), "u.sock")
-        u = socket.socket(socket.AF_UNIX); u.bind(path); u.listen()
-        uc = socket.socket(socket.AF_UNIX); uc.connect(path)
+        # a Unix-domain server in the sandbox's own /tmp (by a relative name:
+        # sun_path holds 108 bytes, the sandbox tree may lie deeper than that)
+        os.chdir(os.environ.get("TMPDIR", "/tmp"))
+        u = socket.socket(socket.AF_UNIX); u.bind("u.sock"); u.listen()
+        uc = socket.socket(socket.AF_UNIX); uc.connect("u.sock")
         a, _ = u.accept(); a.sendall(b"unix ok"); print(uc.recv(16).decode())
     """)
     assert r.exit_code == 0, r.stderr

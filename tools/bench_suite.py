@@ -50,7 +50,8 @@ def main():
         for name, extra in RUNS:
             if a.only and name not in a.only:
                 continue
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--warmup", "2", *extra]
+            # --full: the suite's lines carry CPU per Execute, the executors' figures, the node bound
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--warmup", "2", "--full", *extra]
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout, cwd=ROOT)
             except subprocess.TimeoutExpired:

@@ -23,7 +23,7 @@ for round in $(seq 1 $ROUNDS); do
       elif [ -n "$kv" ]; then envs+=("$kv"); fi
     done
     echo "[cpu_ab] round $round $name ${envs[*]}" >&2
-    line=$(env "${envs[@]}" timeout -k 10 300 python3 $R/bench.py --gpus 1 --steps $STEPS --warmup $WARMUP ${extra[*]} 2>>$R/gpurun_out/cpu_ab.err | grep '^{' | tail -1)
+    line=$(env "${envs[@]}" timeout -k 10 300 python3 $R/bench.py --gpus 1 --steps $STEPS --warmup $WARMUP --full ${extra[*]} 2>>${OUT%.jsonl}.err | grep '^{' | tail -1)
     rc=$?
     if [ $rc -ne 0 ] || [ -z "$line" ]; then echo "[cpu_ab] $name failed rc=$rc" >&2; exit 1; fi
     python3 -c "

@@ -3,7 +3,8 @@ a child process with an optional CPU affinity (inherited by the whole
 service tree) and reports the cgroup's cpu.stat throttling counters around
 it.
 
-    python tools/probe/affinity_ab.py --cpus 16 -- --gpus 1 --steps 20 --warmup 5
+    python tools/probe/affinity_ab.py --cpus 16 -- --gpus 1 --steps 20 --warmup 5 --full
+    (--full: the bench line then carries cpu_ms_per_exec, reported here)
     (--cpus 0: no pinning; N > 0: the first N CPUs of the GPU's NUMA node)
 """
 

@@ -11,7 +11,9 @@ for round in $(seq 1 "$ROUNDS"); do
   for tree in this other; do
     dir=$R; [ "$tree" = other ] && dir=$R/$OTHER
     echo "[tree_ab] round $round $tree" >&2
-    line=$(cd "$dir" && timeout -k 10 300 python3 bench.py --gpus 1 --steps "$STEPS" --warmup "$WARMUP" 2>>"$R/gpurun_out/tree_ab.err" | grep '^{' | tail -1)
+    # --full: CPU / GPU time per Execute, the materialised run and the executors' figures recorded below
+    # (BENCH_ARGS= for a checkout from before that option, whose every run reports them)
+    line=$(cd "$dir" && timeout -k 10 300 python3 bench.py --gpus 1 --steps "$STEPS" --warmup "$WARMUP" ${BENCH_ARGS---full} 2>>"${OUT%.jsonl}.err" | grep '^{' | tail -1)
     rc=$?
     if [ $rc -ne 0 ] || [ -z "$line" ]; then echo "[tree_ab] $tree failed rc=$rc" >&2; exit 1; fi
     python3 -c "
@@ -21,7 +23,7 @@ print(json.dumps({'tree': sys.argv[2], 'round': int(sys.argv[3]), 'steps': int(s
                   'p50': d['p50_latency_ms'], 'p50_in_sandbox': d.get('p50_in_sandbox_exec_ms'), 'errors': d['errors'],
                   'cpu_ms_per_exec': d.get('cpu_ms_per_exec'), 'node_bound': d.get('node_bound'),
                   'gpu_time': d.get('gpu_time'), 'materialized': (d.get('materialized') or {}).get('value'),
-                  'sandbox_cpu': d['executors'][0].get('sandbox_cpu')}))
+                  'sandbox_cpu': (d.get('executors') or [{}])[0].get('sandbox_cpu')}))
 " "$line" "$tree" "$round" "$STEPS" >> "$OUT"
   done
 done
