@@ -41,8 +41,8 @@ STATUS = {
 }
 
 # dtype codes shared with csrc/kernels/bk_common.hpp
-DTYPE_CODES = {"float32": 0, "float64": 1, "bfloat16": 2, "float16": 3, "int32": 4, "int64": 5}
-DTYPE_SIZES = {"float32": 4, "float64": 8, "bfloat16": 2, "float16": 2, "int32": 4, "int64": 8}
+DTYPE_CODES = {"float32": 0, "float64": 1, "bfloat16": 2, "float16": 3, "int32": 4, "int64": 5, "bool": 6}
+DTYPE_SIZES = {"float32": 4, "float64": 8, "bfloat16": 2, "float16": 2, "int32": 4, "int64": 8, "bool": 1}
 
 
 def library_path() -> str:
@@ -99,6 +99,13 @@ def _declare(lib: ctypes.CDLL) -> None:
         "bk_reduce_workspace_bytes": ([], c_int),
         "bk_reduce": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp], c_int),
         "bk_rand_reduce": ([c_int, c_int, c_i64, c_u64, c_u64, c_d, c_d, c_vp, c_vp, c_vp], c_int),
+        "bk_compare": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_vp, c_i64, c_vp], c_int),
+        "bk_compare_count": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_i64, c_vp, c_vp, c_vp], c_int),
+        "bk_mask_logical": ([c_int, c_vp, c_vp, c_vp, c_i64, c_vp], c_int),
+        "bk_where": ([c_int, c_vp, c_int, c_vp, c_vp, c_d, c_d, c_vp, c_i64, c_vp], c_int),
+        "bk_compress_workspace_bytes": ([], c_i64),
+        "bk_compress_workspace_init": ([c_vp, c_vp], c_int),
+        "bk_compress": ([c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
         "bk_reduce_axis_workspace_bytes": ([], c_i64),
         "bk_reduce_workspace_init": ([c_vp, c_vp], c_int),
         "bk_reduce_axis_workspace_init": ([c_vp, c_vp], c_int),

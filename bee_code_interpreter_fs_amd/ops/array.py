@@ -8,6 +8,12 @@ star).  The benchmark payload `examples/benchmark-numpy.py:18-22` becomes::
     x = bk.random.rand(10**8)          # Philox kernel, f64, stays in HBM
     result = bk.sum(bk.square(x))      # fused square+sum: one HBM read pass
 
+Comparisons (``x < 0.5``, ``bk.less_equal(a, b)``) return ``bool`` masks, one
+byte per element as numpy's; a mask is *lazy* too: ``sum`` / ``mean`` /
+``count_nonzero`` / ``any`` / ``all`` of it count in one fused pass over the
+operands (no mask written), any other use (``where``, ``x[mask]``, ``&``)
+materialises it.
+
 ``square`` (and ``x * x`` / ``x ** 2``) returns a *lazy* array: if the only
 consumer is a reduction the square is fused into it (no 800 MB temporary);
 any other use materialises it with the elementwise kernel.
@@ -22,9 +28,10 @@ import math
 import os
 import struct
 import threading
+import weakref
 from typing import Any, Optional, Sequence, Tuple
 
-from ._lazy import is_integer, is_number, np, scalar
+from ._lazy import is_integer, is_number, np, numpy_loaded, scalar
 from ._native import DTYPE_CODES, DTYPE_SIZES, BeekernError, QuotaExceeded  # noqa: F401
 from .driver import make_driver
 
@@ -36,7 +43,12 @@ _UNARY = {
 }
 _BINARY = {"add": 0, "subtract": 1, "multiply": 2, "divide": 3, "maximum": 4, "minimum": 5, "power": 6}
 _REDUCE = {"sum": 0, "square_sum": 1, "abs_sum": 2, "max": 3, "min": 4, "dot": 5, "max_abs_diff": 6}
-_SUPPORTED = ("float32", "float64", "bfloat16")
+# (max and min of a mask are any and all, as 0.0 / 1.0)
+_COMPARE = {"less": 0, "less_equal": 1, "greater": 2, "greater_equal": 3, "equal": 4, "not_equal": 5}
+_FLIPPED = {0: 2, 1: 3, 2: 0, 3: 1, 4: 4, 5: 5}  # s OP x  ==  x FLIPPED[OP] s
+_LOGICAL = {"logical_and": 0, "logical_or": 1, "logical_xor": 2, "logical_not": 3}
+_SUPPORTED = ("float32", "float64", "bfloat16", "bool")
+_FLOATS = ("float32", "float64", "bfloat16")
 
 _state_lock = threading.Lock()
 _driver = None
@@ -45,6 +57,8 @@ _driver = None
 def normalize_dtype(dtype: Any) -> str:
     if dtype is None:
         return "float64"
+    if dtype is bool:
+        return "bool"
     if isinstance(dtype, str):
         name = {"bf16": "bfloat16", "f32": "float32", "f64": "float64", "double": "float64", "float": "float64"}.get(
             dtype, dtype
@@ -114,10 +128,11 @@ def device_info() -> dict:
 class _Buffer:
     """Owns one device allocation (pointer or broker handle)."""
 
-    __slots__ = ("ptr", "nbytes", "_owner", "_drv", "__weakref__")
+    __slots__ = ("ptr", "nbytes", "_owner", "_drv", "_readers", "__weakref__")
 
     def __init__(self, nbytes: int, ptr: Optional[int] = None, owner: Any = None) -> None:
         self.nbytes = int(nbytes)
+        self._readers = None  # lazy masks that still have to read this buffer (a WeakSet, on first use)
         self._owner = owner
         self._drv = driver()
         self.ptr = int(ptr) if ptr is not None else self._drv.malloc(max(self.nbytes, 1))
@@ -138,8 +153,9 @@ class DeviceArray:
     def __init__(self, shape: Sequence[int], dtype: str, buffer: Optional[_Buffer] = None, lazy=None, strides_t=False):
         self.shape: Shape = tuple(int(s) for s in shape)
         self.dtype = normalize_dtype(dtype)
-        # until materialised: ("square", src), or ("rand", kind, seed, offset,
-        # lo, hi) -- a draw whose values are fixed by its counter range
+        # until materialised: ("square", src), ("rand", kind, seed, offset,
+        # lo, hi) -- a draw whose values are fixed by its counter range -- or
+        # ("cmp", op, a, b_or_scalar): a mask of a comparison not yet run
         self._lazy = lazy
         self._transposed = strides_t  # 2-D transposed view of a contiguous buffer
         if buffer is None and lazy is None:
@@ -186,6 +202,13 @@ class DeviceArray:
                 _, kind, seed, off, lo, hi = self._lazy
                 self._buf = _Buffer(self.nbytes)
                 driver().rand(kind, self._buf.ptr, self.size, self.code, seed, off, lo, hi)
+            elif self._lazy[0] == "cmp":
+                _, op, a, b = self._lazy
+                self._buf = _Buffer(self.nbytes)
+                if isinstance(b, DeviceArray):
+                    driver().compare(op, a.code, 0, a.ptr, b.ptr, 0.0, self._buf.ptr, self.size)
+                else:
+                    driver().compare(op, a.code, 1, a.ptr, 0, b, self._buf.ptr, self.size)
             else:
                 op, src = self._lazy
                 self._buf = _Buffer(self.nbytes)
@@ -255,13 +278,43 @@ class DeviceArray:
         dt = normalize_dtype(dtype)
         if dt == self.dtype:
             return self.copy()
+        if "bool" in (dt, self.dtype):
+            if dt not in ("float32", "float64"):
+                raise TypeError(f"beekern astype: {self.dtype} -> {dt} has no kernel (bool converts to float32 / float64)")
+            if driver().name == "broker":
+                # the broker's CAST frame knows float dtypes only
+                # (broker_core.cpp dtype_size): the same values through WHERE
+                return where(self, 1.0, 0.0, dtype=dt)
         self._materialize()
         out = DeviceArray(self.shape, dt)
         driver().cast(self.code, out.code, self.ptr, out.ptr, self.size)
         return out
 
     def copy(self) -> "DeviceArray":
+        if self.dtype == "bool":
+            out = DeviceArray(self.shape, "bool")
+            driver().copy(out.ptr, self.ptr, self.nbytes)
+            return out
         return _unary("copy", self)
+
+    def any(self) -> bool:
+        return any(self)
+
+    def all(self) -> bool:
+        return all(self)
+
+    def __getitem__(self, key) -> "DeviceArray":
+        """``x[mask]``: the elements where the bool array ``mask`` (of x's
+        shape) is true, 1-D in C order.  No other indexing on the device."""
+        if not isinstance(key, DeviceArray) or key.dtype != "bool":
+            raise TypeError("beekern arrays are indexed by a bool DeviceArray of the same shape only")
+        if key.shape != self.shape:
+            raise TypeError(f"beekern x[mask]: the mask's shape {key.shape} is not the array's {self.shape}")
+        count = count_nonzero(key)  # (a lazy mask: the fused count)
+        out = DeviceArray((count,), self.dtype)
+        if count:
+            driver().compress(self.code, self.ptr, key.ptr, self.size, out.ptr, count)
+        return out
 
     def sum(self, axis: Optional[int] = None):
         return sum(self, axis)
@@ -293,6 +346,18 @@ class DeviceArray:
     def __neg__(self): return _unary("negative", self)
     def __abs__(self): return _unary("abs", self)
     def __matmul__(self, o): return matmul(self, o)
+    # (== and != stay identity-based, as object's)
+    def __lt__(self, o): return less(self, o)
+    def __le__(self, o): return less_equal(self, o)
+    def __gt__(self, o): return greater(self, o)
+    def __ge__(self, o): return greater_equal(self, o)
+    def __and__(self, o): return logical_and(self, o)
+    def __rand__(self, o): return logical_and(o, self)
+    def __or__(self, o): return logical_or(self, o)
+    def __ror__(self, o): return logical_or(o, self)
+    def __xor__(self, o): return logical_xor(self, o)
+    def __rxor__(self, o): return logical_xor(o, self)
+    def __invert__(self): return logical_not(self)
 
 
 _BINDING = []
@@ -312,11 +377,12 @@ def _binding():
 
 
 def _np_dtype(dtype: str):
-    return {"float32": np.float32, "float64": np.float64}[dtype]
+    return {"float32": np.float32, "float64": np.float64, "bool": np.bool_}[dtype]
 
 
 def _np_view_dtype(dtype: str):
-    return np.uint16 if dtype == "bfloat16" else _np_dtype(dtype)
+    # (a mask's bytes come down as uint8: a buffer may hold any non-zero byte for true)
+    return np.uint16 if dtype == "bfloat16" else np.uint8 if dtype == "bool" else _np_dtype(dtype)
 
 
 def _download(buf: _Buffer, shape: Shape, dtype: str) -> np.ndarray:
@@ -324,6 +390,8 @@ def _download(buf: _Buffer, shape: Shape, dtype: str) -> np.ndarray:
     driver().d2h(buf.ptr, host)
     if dtype == "bfloat16":
         return (host.astype(np.uint32) << 16).view(np.float32)
+    if dtype == "bool":
+        return host != 0
     return host
 
 
@@ -362,7 +430,9 @@ def empty(shape, dtype="float64") -> DeviceArray:
 def full(shape, value: float, dtype="float64") -> DeviceArray:
     a = empty(shape, dtype)
     # the fill's bit pattern (no numpy: see ops/_lazy.py)
-    if a.dtype == "float64":
+    if a.dtype == "bool":
+        pattern, width = (1 if value else 0), 1
+    elif a.dtype == "float64":
         pattern, width = struct.unpack("<Q", struct.pack("<d", float(value)))[0], 8
     elif a.dtype == "float32":
         pattern, width = struct.unpack("<I", struct.pack("<f", float(value)))[0], 4
@@ -432,8 +502,16 @@ def _as_operand(x) -> DeviceArray:
     return x if isinstance(x, DeviceArray) else asarray(x)
 
 
+def _no_masks(what: str, *arrays) -> None:
+    for a in arrays:
+        if a.dtype == "bool":
+            raise TypeError(f"beekern {what}: no kernel for bool arrays (masks take logical_* / where / astype)")
+
+
 def _unary(op: str, x) -> DeviceArray:
-    x = _as_operand(x)._materialize()
+    x = _as_operand(x)
+    _no_masks(op, x)
+    x._materialize()
     out = DeviceArray(x.shape, x.dtype)
     driver().unary(_UNARY[op], x.code, x.ptr, out.ptr, x.size)
     return out
@@ -450,12 +528,16 @@ def square(x) -> DeviceArray:
 
 
 def _binary(op: str, a, b, reversed_: bool = False) -> DeviceArray:
-    a = _as_operand(a)._materialize()
+    a = _as_operand(a)
+    _no_masks(op, a)
+    a._materialize()
     if is_number(b):
         out = DeviceArray(a.shape, a.dtype)
         driver().binary(_BINARY[op], a.code, 2 if reversed_ else 1, a.ptr, 0, float(b), out.ptr, a.size)
         return out
-    b = _as_operand(b)._materialize()
+    b = _as_operand(b)
+    _no_masks(op, b)
+    b._materialize()
     if b.shape != a.shape or b.dtype != a.dtype:
         if b.size == 1:
             return _binary(op, a, float(b.item()), reversed_)
@@ -508,6 +590,12 @@ def _reduce_axis(op: str, x: DeviceArray, axis: int):
 
 def sum(x, axis: Optional[int] = None):  # noqa: A001 - numpy-compatible name
     x = _as_operand(x)
+    if x.dtype == "bool":
+        if axis is not None and not (x.ndim == 1 and axis in (0, -1)):
+            raise TypeError("beekern sum: axis sums of a bool array have no kernel")
+        count = count_nonzero(x)
+        m = numpy_loaded()
+        return m.int64(count) if m is not None else count
     if axis is not None:
         return _reduce_axis("sum", x, int(axis))
     if x._lazy is not None and x._lazy[0] == "square":
@@ -529,6 +617,10 @@ def square_sum(x) -> np.float64:
 
 def mean(x, axis: Optional[int] = None):
     x = _as_operand(x)
+    if x.dtype == "bool":
+        if axis is not None and not (x.ndim == 1 and axis in (0, -1)):
+            raise TypeError("beekern mean: axis means of a bool array have no kernel")
+        return scalar(count_nonzero(x) / x.size) if x.size else scalar(float("nan"))
     if axis is not None:
         return _reduce_axis("mean", x, int(axis))
     return sum(x) / x.size
@@ -584,6 +676,183 @@ def divide(a, b): return _binary("divide", a, b)
 def maximum(a, b): return _binary("maximum", a, b)
 def minimum(a, b): return _binary("minimum", a, b)
 def power(a, b): return _binary("power", a, b)
+
+
+# ---- boolean masks -------------------------------------------------------------------
+
+def _is_numpy_scalar(s) -> bool:
+    m = numpy_loaded()
+    return m is not None and isinstance(s, (m.floating, m.integer, m.bool_))
+
+
+def _round_to(s: float, dtype: str) -> float:
+    """A Python scalar as the array's dtype would hold it (numpy 2: Python
+    numbers are weak and take the array's dtype), as a double."""
+    if dtype == "float64":
+        return s
+    try:
+        bits = struct.unpack("<I", struct.pack("<f", s))[0]  # RNE
+    except OverflowError:  # past float32's range: +-inf, as numpy's cast
+        return math.copysign(math.inf, s)
+    if dtype == "bfloat16":
+        bits = _f32_bits_to_bf16(bits) << 16
+    return struct.unpack("<f", struct.pack("<I", bits))[0]
+
+
+def _compare_scalar(s, dtype: str) -> float:
+    """The double the comparison kernel compares every (widened) element
+    with.  A Python number is rounded to the array's dtype first; a numpy
+    scalar goes unrounded -- where it would promote (np.float64 against an
+    f32 array) the kernel's f64 comparison is numpy's promoted one, and where
+    it would not, it is exact in the dtype already."""
+    if _is_numpy_scalar(s):
+        return float(s)
+    return _round_to(float(s), dtype)
+
+
+def _scalar_keeps_dtype(s, dtype: str) -> bool:
+    """Whether numpy's result stays in ``dtype`` when ``s`` meets such an array."""
+    if not _is_numpy_scalar(s):
+        return True
+    return dtype != "bfloat16" and np.result_type(np.dtype(dtype), s) == np.dtype(dtype)
+
+
+def _compare(op: str, a, b) -> DeviceArray:
+    code = _COMPARE[op]
+    if not isinstance(a, DeviceArray):
+        if not isinstance(b, DeviceArray):
+            raise TypeError(f"beekern {op}: one operand must be a DeviceArray")
+        a, b, code = b, a, _FLIPPED[code]  # scalar OP array: the flipped operator
+    if a.dtype not in _FLOATS:
+        raise TypeError(f"beekern {op}: float arrays only, got {a.dtype}")
+    if not (a._lazy is None and not a._transposed):
+        a._materialize()
+    if isinstance(b, DeviceArray):
+        if b.shape != a.shape or b.dtype != a.dtype:
+            if b.size == 1 and b.dtype in _FLOATS:
+                return _compare(op, a, float(b.item()))
+            raise ValueError(f"beekern {op}: shapes/dtypes must match ({a.shape} {a.dtype} vs {b.shape} {b.dtype})")
+        b._materialize()
+        other = b
+    elif is_number(b) or _is_numpy_scalar(b):
+        other = _compare_scalar(b, a.dtype)
+    else:
+        raise TypeError(f"beekern {op}: cannot compare a DeviceArray with {type(b).__name__}")
+    mask = DeviceArray(a.shape, "bool", lazy=("cmp", code, a, other))
+    for src in (a, other):
+        if isinstance(src, DeviceArray):
+            if src._buf._readers is None:
+                src._buf._readers = weakref.WeakSet()
+            src._buf._readers.add(mask)
+    return mask
+
+
+def _before_write(target: DeviceArray) -> None:
+    """An in-place write into ``target`` is about to be enqueued: the lazy
+    masks that still have to read its buffer run first (they are snapshots
+    of the values at the time of the comparison)."""
+    readers = target._buf._readers if target._buf is not None else None
+    if readers:
+        for m in list(readers):
+            m._materialize()
+        readers.clear()
+
+
+def less(a, b): return _compare("less", a, b)
+def less_equal(a, b): return _compare("less_equal", a, b)
+def greater(a, b): return _compare("greater", a, b)
+def greater_equal(a, b): return _compare("greater_equal", a, b)
+def equal(a, b): return _compare("equal", a, b)
+def not_equal(a, b): return _compare("not_equal", a, b)
+
+
+def _is_lazy_mask(m: DeviceArray) -> bool:
+    return m._lazy is not None and m._lazy[0] == "cmp"
+
+
+def count_nonzero(x) -> int:
+    """The number of true (non-zero) elements.  A lazy mask, or a float array
+    (``x != 0``), is counted in one fused pass with no mask written."""
+    x = _as_operand(x)
+    if x.dtype != "bool":
+        x = _compare("not_equal", x, 0.0)
+    if _is_lazy_mask(x):
+        _, op, a, b = x._lazy
+        if isinstance(b, DeviceArray):
+            return int(driver().compare_count(op, a.code, 0, a.ptr, b.ptr, 0.0, x.size))
+        return int(driver().compare_count(op, a.code, 1, a.ptr, 0, b, x.size))
+    return int(driver().reduce(_REDUCE["sum"], x.code, x.ptr, 0, x.size))
+
+
+def _mask_operand(what: str, m) -> DeviceArray:
+    if not isinstance(m, DeviceArray) or m.dtype != "bool":
+        raise TypeError(f"beekern {what}: bool DeviceArrays only, got "
+                        f"{m.dtype if isinstance(m, DeviceArray) else type(m).__name__}")
+    return m
+
+
+def any(x) -> bool:  # noqa: A001 - numpy-compatible name
+    x = _mask_operand("any", x)
+    if _is_lazy_mask(x):
+        return count_nonzero(x) > 0
+    return driver().reduce(_REDUCE["max"], x.code, x.ptr, 0, x.size) != 0.0
+
+
+def all(x) -> bool:  # noqa: A001 - numpy-compatible name
+    x = _mask_operand("all", x)
+    if _is_lazy_mask(x):
+        return count_nonzero(x) == x.size
+    return driver().reduce(_REDUCE["min"], x.code, x.ptr, 0, x.size) != 0.0
+
+
+def _logical(op: str, a, b=None) -> DeviceArray:
+    a = _mask_operand(op, a)
+    if b is not None:
+        b = _mask_operand(op, b)
+        if b.shape != a.shape:
+            raise ValueError(f"beekern {op}: shapes must match ({a.shape} vs {b.shape})")
+    out = DeviceArray(a.shape, "bool")
+    driver().mask_logical(_LOGICAL[op], a.ptr, b.ptr if b is not None else 0, out.ptr, a.size)
+    return out
+
+
+def logical_and(a, b): return _logical("logical_and", a, b)
+def logical_or(a, b): return _logical("logical_or", a, b)
+def logical_xor(a, b): return _logical("logical_xor", a, b)
+def logical_not(a): return _logical("logical_not", a)
+
+
+def where(mask, a, b, dtype=None) -> DeviceArray:
+    """``mask ? a : b`` elementwise.  ``a`` and ``b``: device arrays of the
+    mask's shape (one float dtype), or scalars; a Python number takes the
+    arrays' dtype, two scalars give float64 (or ``dtype``).  Array values are
+    moved as bits (NaN payloads and -0.0 survive)."""
+    mask = _mask_operand("where", mask)
+    arrays = [v for v in (a, b) if isinstance(v, DeviceArray)]
+    for v in (a, b):
+        if not isinstance(v, DeviceArray) and not (is_number(v) or _is_numpy_scalar(v)):
+            raise TypeError(f"beekern where: operands are DeviceArrays or numbers, got {type(v).__name__}")
+    if arrays:
+        dt = arrays[0].dtype
+        for v in arrays:
+            if v.dtype != dt or v.dtype not in _FLOATS:
+                raise TypeError(f"beekern where: arrays of one float dtype, got {[x.dtype for x in arrays]}")
+            if v.shape != mask.shape:
+                raise ValueError(f"beekern where: shapes must match the mask's ({v.shape} vs {mask.shape})")
+        if dtype is not None and normalize_dtype(dtype) != dt:
+            raise TypeError("beekern where: dtype= is for two scalars")
+    else:
+        dt = normalize_dtype(dtype) if dtype is not None else "float64"
+        if dt not in _FLOATS:
+            raise TypeError(f"beekern where: float results only, got {dt}")
+    for v in (a, b):
+        if not isinstance(v, DeviceArray) and arrays and not _scalar_keeps_dtype(v, dt):
+            raise TypeError(f"beekern where: a {type(v).__name__} scalar would promote the {dt} result")
+    flags = (0 if isinstance(a, DeviceArray) else 1) | (0 if isinstance(b, DeviceArray) else 2)
+    out = DeviceArray(mask.shape, dt)
+    driver().where(DTYPE_CODES[dt], mask.ptr, flags, a.ptr if not flags & 1 else 0, b.ptr if not flags & 2 else 0,
+                   float(a) if flags & 1 else 0.0, float(b) if flags & 2 else 0.0, out.ptr, mask.size)
+    return out
 
 
 # ---- matmul --------------------------------------------------------------------------

@@ -41,6 +41,7 @@ class NativeDriver:
         self.ws = 0
         self.scalar = 0
         self.axis_ws = 0
+        self.compress_ws = 0
 
     def init(self, device: int) -> None:
         check(self.lib.bk_init(int(device)), "bk_init")
@@ -126,6 +127,36 @@ class NativeDriver:
         check(self.lib.bk_reduce_axis(op, dt, _vp(x), rows, cols, ld, axis, _vp(y), _vp(self.axis_ws), self.stream),
               "bk_reduce_axis")
 
+    # ---- boolean masks (csrc/kernels/mask.hip): one byte per element ----------------
+    def compare(self, op: int, dt: int, mode: int, a: int, b: int, sc: float, y: int, n: int) -> None:
+        """y[i] = a[i] OP (b[i] | sc) as 0 / 1 bytes; op 0 < 1 <= 2 > 3 >= 4 == 5 !=; mode 0 array, 1 scalar."""
+        check(self.lib.bk_compare(op, dt, mode, _vp(a), _vp(b) if b else None, sc, _vp(y), n, self.stream), "bk_compare")
+
+    def compare_count(self, op: int, dt: int, mode: int, a: int, b: int, sc: float, n: int) -> float:
+        """The number of true comparisons, no mask written (one fused launch)."""
+        check(self.lib.bk_compare_count(op, dt, mode, _vp(a), _vp(b) if b else None, sc, n, _vp(self.ws),
+                                        _vp(self.scalar), self.stream), "bk_compare_count")
+        out = np.zeros(1, np.float64)
+        self.d2h(self.scalar, out)
+        return float(out[0])
+
+    def mask_logical(self, op: int, a: int, b: int, y: int, n: int) -> None:
+        """op 0 and, 1 or, 2 xor, 3 not (b unused)."""
+        check(self.lib.bk_mask_logical(op, _vp(a), _vp(b) if b else None, _vp(y), n, self.stream), "bk_mask_logical")
+
+    def where(self, dt: int, mask: int, flags: int, a: int, b: int, sa: float, sb: float, y: int, n: int) -> None:
+        """y[i] = mask[i] ? A : B; flags bit 0: A is the scalar sa, bit 1: B is the scalar sb."""
+        check(self.lib.bk_where(dt, _vp(mask), flags, _vp(a) if a else None, _vp(b) if b else None, sa, sb, _vp(y), n,
+                                self.stream), "bk_where")
+
+    def compress(self, dt: int, x: int, mask: int, n: int, y: int, cap: int) -> None:
+        """y[0:cap] = x[mask] in index order (writes past cap are dropped)."""
+        if not self.compress_ws:
+            self.compress_ws = self.malloc(self.lib.bk_compress_workspace_bytes())
+            check(self.lib.bk_compress_workspace_init(_vp(self.compress_ws), self.stream), "bk_compress_workspace_init")
+        check(self.lib.bk_compress(dt, _vp(x), _vp(mask), n, _vp(y), cap, _vp(self.compress_ws), self.stream),
+              "bk_compress")
+
     def transpose(self, src: int, dst: int, rows: int, cols: int, ldi: int, ldo: int, src_dtype: int = 2,
                   dst_dtype: int = 2) -> None:
         check(self.lib.bk_transpose(src_dtype, dst_dtype, _vp(src), _vp(dst), rows, cols, ldi, ldo, self.stream),
@@ -184,7 +215,8 @@ def _info_dict(v, arch: str) -> dict:
 # ---- broker client --------------------------------------------------------------------
 
 (HELLO, ALLOC, FREE, WRITE, READ, RAND, UNARY, BINARY, CAST, FILL, REDUCE, GEMM, TRANSPOSE, SYNC, MEMSTATS, INFO,
- COPY, RAND_REDUCE, ALLOC_AT, REDUCE_AXIS, GEMM_FP) = range(1, 22)
+ COPY, RAND_REDUCE, ALLOC_AT, REDUCE_AXIS, GEMM_FP, COMPARE, COMPARE_COUNT, MASK_LOGICAL, WHERE,
+ COMPRESS) = range(1, 27)
 _HDR = struct.Struct("<IIQ")
 _NO_REPLY = 1  # request flag: no response unless a later request collects an error
 _RHDR = struct.Struct("<iIQ")
@@ -424,6 +456,23 @@ class BrokerDriver:
 
     def reduce_axis(self, op, dt, x, y, rows, cols, ld, axis) -> None:
         self._post(REDUCE_AXIS, struct.pack("<IIQQqqqII", op, dt, x, y, rows, cols, ld, axis, 0))
+
+    # boolean masks: payload layouts beside the op enum in csrc/executor/broker_core.hpp
+    def compare(self, op, dt, mode, a, b, sc, y, n) -> None:
+        self._post(COMPARE, struct.pack("<IIIIQQdQq", op, dt, mode, 0, a, b or 0, sc, y, n))
+
+    def compare_count(self, op, dt, mode, a, b, sc, n) -> float:
+        payload = struct.pack("<IIIIQQdq", op, dt, mode, 0, a, b or 0, sc, n)
+        return struct.unpack("<d", self._call(COMPARE_COUNT, payload))[0]
+
+    def mask_logical(self, op, a, b, y, n) -> None:
+        self._post(MASK_LOGICAL, struct.pack("<IIQQQq", op, 0, a, b or 0, y, n))
+
+    def where(self, dt, mask, flags, a, b, sa, sb, y, n) -> None:
+        self._post(WHERE, struct.pack("<IIQQQddQq", dt, flags, mask, a or 0, b or 0, sa, sb, y, n))
+
+    def compress(self, dt, x, mask, n, y, cap) -> None:
+        self._post(COMPRESS, struct.pack("<IIQQqQq", dt, 0, x, mask, n, y, cap))
 
     def transpose(self, src, dst, rows, cols, ldi, ldo, src_dtype=2, dst_dtype=2) -> None:
         self._post(TRANSPOSE, struct.pack("<QQiiiiii", src, dst, rows, cols, ldi, ldo, src_dtype, dst_dtype))

@@ -8,6 +8,16 @@ what numpy would (same dtype rules, same shape):
   subtract, multiply, divide, maximum, minimum, power -- elementwise kernels
   (``ops/array.py`` ``_unary`` / ``_binary``); ``np.square`` stays lazy, so
   ``np.sum(np.square(x))`` is the fused one-pass square-sum;
+* comparisons ``less`` / ``less_equal`` / ``greater`` / ``greater_equal`` /
+  ``equal`` / ``not_equal`` of two device arrays or an array and a scalar
+  (either side): a device ``bool`` mask, lazy until something other than a
+  count needs it, so ``np.sum(x * x + y * y <= 1.0)`` is one fused
+  compare-count pass (``csrc/kernels/mask.hip``); a Python number is rounded
+  to the array's dtype first and a numpy scalar that would promote compares
+  in f64, as numpy 2 does;
+* on ``bool`` masks: ``logical_and`` / ``logical_or`` / ``logical_xor`` /
+  ``logical_not`` and ``bitwise_and`` / ``bitwise_or`` / ``bitwise_xor`` /
+  ``invert`` (``&``, ``|``, ``^``, ``~``);
 * ufunc reductions ``np.add.reduce`` / ``np.maximum.reduce`` /
   ``np.minimum.reduce``;
 * functions: ``sum`` / ``mean`` (whole array or one axis of a 2-D array),
@@ -15,6 +25,9 @@ what numpy would (same dtype rules, same shape):
   ``std`` (two passes, as numpy), ``linalg.norm`` (fused square-sum),
   ``copy`` / ``reshape`` / ``ravel``, and the metadata functions
   ``shape`` / ``ndim`` / ``size``;
+* masks: ``sum`` (``np.int64``) / ``mean`` / ``count_nonzero`` (also of a
+  float array: the fused ``!= 0`` count) / ``any`` / ``all`` of a whole
+  array, and the three-argument ``where(mask, x, y)``;
 * ``matmul`` / ``dot`` / ``@`` of 1-D and 2-D operands: f32 / f64 on the
   full-precision MFMA GEMM in numpy's result dtype (``ops/array.py``
   ``matmul_fp``, ``csrc/kernels/gemm_fp.hip``; ``.T`` views read in place),
@@ -70,6 +83,11 @@ _UNARY = {"square": "square", "negative": "negative", "absolute": "abs", "sqrt":
 _BINARY = {"add": "add", "subtract": "subtract", "multiply": "multiply", "divide": "divide",
            "true_divide": "divide", "maximum": "maximum", "minimum": "minimum", "power": "power"}
 _REDUCE = {"add": "sum", "maximum": "amax", "minimum": "amin"}
+_COMPARE = ("less", "less_equal", "greater", "greater_equal", "equal", "not_equal")
+# on bool masks the bitwise ufuncs are the logical ones
+_LOGICAL = {"logical_and": "logical_and", "logical_or": "logical_or", "logical_xor": "logical_xor",
+            "logical_not": "logical_not", "bitwise_and": "logical_and", "bitwise_or": "logical_or",
+            "bitwise_xor": "logical_xor", "invert": "logical_not"}
 
 
 class Binding:
@@ -96,7 +114,12 @@ def _weak_scalar_ok(s, dtype_name: str) -> bool:
 
 
 def _as_result_scalar(v, dtype_name: str):
-    """numpy types a full reduction by the array's dtype (f32 -> float32)."""
+    """numpy types a full reduction by the array's dtype (f32 -> float32); of
+    a bool mask: a count is int64, a mean float64, any / all bool."""
+    if dtype_name == "bool":
+        if isinstance(v, (bool, np.bool_)):
+            return np.bool_(v)
+        return np.int64(v) if isinstance(v, (int, np.integer)) else np.float64(v)
     if dtype_name == "float32":
         return np.float32(v)
     return np.float64(v)
@@ -187,6 +210,7 @@ def array_ufunc(b: Binding, ufunc, method: str, inputs, kwargs):
     if res is not None:
         if out is not None:
             target = b.dev(out[0])
+            A._before_write(target)  # (lazy masks of the old values run first)
             A.driver().unary(A._UNARY["copy"], target.code, res.ptr, target.ptr, target.size)
             return out[0]
         return b.box(res) if isinstance(res, A.DeviceArray) else res
@@ -214,6 +238,10 @@ def _try_ufunc(b, A, ufunc, name, method, inputs, kwargs, extra) -> Optional[Any
             return None
         if any(d.dtype != dt for d in arrays):
             return None
+        if name in _COMPARE or name in _LOGICAL or dt == "bool":
+            if out is not None or kwargs.get("dtype") is not None:
+                return None
+            return _try_mask_ufunc(A, name, inputs, devs, dt)
         if out is not None:
             if len(out) != 1 or b.dev(out[0]) is None:
                 return None
@@ -254,7 +282,36 @@ def _try_ufunc(b, A, ufunc, name, method, inputs, kwargs, extra) -> Optional[Any
     return None
 
 
+def _try_mask_ufunc(A, name, inputs, devs, dt) -> Optional[Any]:
+    """A comparison of float arrays, or mask logic on bool arrays: the device
+    mask, or None for a host fallback."""
+    if name in _COMPARE and len(inputs) == 2 and dt != "bool":
+        x, y = devs
+        if x is not None and y is not None:
+            return A._compare(name, x, y) if x.shape == y.shape else None
+        arr, s, rev = (x, inputs[1], False) if x is not None else (y, inputs[0], True)
+        if isinstance(s, (np.floating, np.integer, np.bool_)):
+            # weak or strong, the kernel compares in f64: a promoting numpy
+            # scalar (np.float64 against f32) goes unrounded -- numpy's
+            # promoted comparison (wider than f64: numpy on the host)
+            if s.dtype.itemsize > 8:
+                return None
+        elif not _weak_scalar_ok(s, dt):
+            return None
+        return A._compare(name, s, arr) if rev else A._compare(name, arr, s)
+    if name in _LOGICAL and dt == "bool":
+        if any(d is None for d in devs):
+            return None  # (a scalar or host operand)
+        if len(devs) == 1 and _LOGICAL[name] == "logical_not":
+            return A.logical_not(devs[0])
+        if len(devs) == 2 and _LOGICAL[name] != "logical_not" and devs[0].shape == devs[1].shape:
+            return A._logical(_LOGICAL[name], devs[0], devs[1])
+    return None
+
+
 def _full_reduce(A, what: str, x):
+    if x.dtype == "bool":  # numpy: add.reduce counts (int64), max / min are any / all
+        return _as_result_scalar(A.sum(x) if what == "sum" else A.any(x) if what == "amax" else A.all(x), "bool")
     v = A.sum(x) if what == "sum" else A.amax(x) if what == "amax" else A.amin(x)
     return _as_result_scalar(v, x.dtype)
 
@@ -316,6 +373,8 @@ def _try_function(b, A, name, mod, args, kwargs):
         if axis is None or (x.ndim == 1 and axis in (0, -1)):
             v = A.sum(x) if name == "sum" else A.mean(x)
             return _as_result_scalar(v, x.dtype)
+        if x.dtype == "bool":
+            return _NO
         if x.ndim == 2 and isinstance(axis, int) and axis in (0, 1, -1, -2):
             return b.box(A.sum(x, axis=axis) if name == "sum" else A.mean(x, axis=axis))
         return _NO
@@ -333,7 +392,7 @@ def _try_function(b, A, name, mod, args, kwargs):
             return _NO
         x = b.dev(got["a"])
         ddof = got.get("ddof", 0) if _given(got.get("ddof")) else 0
-        if x is None or x.dtype == "bfloat16" or not isinstance(ddof, (int, float)):
+        if x is None or x.dtype in ("bfloat16", "bool") or not isinstance(ddof, (int, float)):
             return _NO
         n = x.size
         if n - ddof <= 0:
@@ -346,7 +405,7 @@ def _try_function(b, A, name, mod, args, kwargs):
         if got is None or not _kw_only(got, {"x"}):
             return _NO
         x = b.dev(got["x"])
-        if x is None:
+        if x is None or x.dtype == "bool":
             return _NO
         return _as_result_scalar(math.sqrt(float(A.square_sum(x))), x.dtype)
     if name in ("dot", "vdot", "inner"):
@@ -354,12 +413,56 @@ def _try_function(b, A, name, mod, args, kwargs):
             return _NO
         x, y = b.dev(args[0]), b.dev(args[1])
         if x is not None and y is not None and x.ndim == 1 and y.ndim == 1 and x.shape == y.shape and \
-                x.dtype == y.dtype:
+                x.dtype == y.dtype and x.dtype != "bool":
             return _as_result_scalar(A.dot(x, y), x.dtype)
         if name == "dot":
             r = _matmul(b, A, args[0], args[1], "dot")
             return _NO if r is None else b.box(r)
         return _NO
+    if name in ("count_nonzero", "any", "all"):
+        params = ("a", "axis") if name == "count_nonzero" else ("a", "axis", "out")
+        got = _bind(name, args, kwargs, params)
+        if got is None or not _kw_only(got, {"a"}):
+            return _NO
+        x = b.dev(got["a"])
+        if x is None:
+            return _NO
+        if name == "count_nonzero":  # (of a float array: the fused != 0 count)
+            return A.count_nonzero(x)
+        count = A.count_nonzero(x) if x.dtype != "bool" else None
+        if name == "any":
+            return np.bool_(count > 0 if count is not None else A.any(x))
+        return np.bool_(count == x.size if count is not None else A.all(x))
+    if name == "where":
+        if len(args) != 3 or kwargs:
+            return _NO  # (the one-argument form is nonzero(): host)
+        cond = b.dev(args[0])
+        if cond is None or cond.dtype != "bool":
+            return _NO
+        vals = []
+        for v in args[1:]:
+            if b.is_mine(v):
+                d = b.dev(v)
+                if d is None:
+                    return _NO  # a host-resident operand: everything stays on the host
+                vals.append(d)
+            elif isinstance(v, (bool, int, float, np.floating, np.integer, np.bool_)):
+                vals.append(v)
+            else:
+                return _NO
+        arrays = [v for v in vals if isinstance(v, A.DeviceArray)]
+        dtype = None
+        if arrays:
+            if not all(_weak_scalar_ok(v, arrays[0].dtype) for v in vals if not isinstance(v, A.DeviceArray)):
+                return _NO
+        else:
+            dtype = np.result_type(*vals).name
+            if dtype not in _FP:
+                return _NO  # (two integers: an integer result, numpy's on the host)
+        try:
+            return b.box(A.where(cond, vals[0], vals[1], dtype=dtype))
+        except (TypeError, ValueError):
+            return _NO
     if name == "copy" and len(args) == 1 and not kwargs:
         x = b.dev(args[0])
         return _NO if x is None else b.box(x.copy())

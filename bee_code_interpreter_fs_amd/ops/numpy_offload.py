@@ -27,7 +27,13 @@ What the user sees:
 * types: an OffloadArray is not an ``ndarray`` subclass; it has ``shape``,
   ``dtype`` (a numpy dtype), ``ndim``, ``size``, the reductions as methods,
   arithmetic operators, and every other ndarray attribute through a host copy;
-* semantics: the first operation without a GPU kernel (indexing, slicing,
+* masks: comparisons of device-resident arrays (``x < 0.5``, ``a >= b``)
+  return device-resident ``bool`` OffloadArrays; ``&`` / ``|`` / ``^`` / ``~``,
+  ``np.sum`` / ``np.mean`` / ``np.count_nonzero`` / ``.any()`` / ``.all()``,
+  ``np.where(mask, x, y)``, ``mask.astype(float)`` and ``x[mask]`` (the mask a
+  device-resident bool OffloadArray of x's shape) stay on the device, so
+  ``np.sum(x**2 + y**2 <= 1.0)`` counts in one fused pass;
+* semantics: the first operation without a GPU kernel (any other indexing, slicing,
   printing, ``np.sort`` ...) copies the array to the host once and keeps it
   there -- from then on it is an ndarray in all but name (views alias it,
   in-place writes stick), with one ``HostFallbackWarning`` per function;
@@ -72,7 +78,7 @@ class _Residency:
 
 
 class OffloadArray:
-    """A float64 / float32 numpy-like array resident on the GPU until an
+    """A float64 / float32 / bool numpy-like array resident on the GPU until an
     operation without a kernel moves it to the host for good."""
 
     __array_priority__ = 1000
@@ -206,6 +212,12 @@ class OffloadArray:
     def dot(self, other):
         return np.dot(self, other)
 
+    def any(self, axis=None, **kw):
+        return np.any(self, axis=axis, **kw)
+
+    def all(self, axis=None, **kw):
+        return np.all(self, axis=axis, **kw)
+
     def copy(self, order="C"):
         return np.copy(self) if order in ("C", "K", "A") else self._h().copy(order)
 
@@ -260,6 +272,11 @@ class OffloadArray:
         return iter(self._h())
 
     def __getitem__(self, key):
+        # x[mask] with both on the device: stream compaction (bk_compress)
+        d = self._dev
+        k = key._dev if isinstance(key, OffloadArray) else None
+        if d is not None and k is not None and k.dtype == "bool" and k.shape == d.shape:
+            return OffloadArray(d[k])
         return self._h()[key]
 
     def __setitem__(self, key, value):
@@ -332,6 +349,13 @@ class OffloadArray:
     def __ge__(self, o): return np.greater_equal(self, o)
     def __eq__(self, o): return np.equal(self, o)
     def __ne__(self, o): return np.not_equal(self, o)
+    def __and__(self, o): return np.bitwise_and(self, o)
+    def __rand__(self, o): return np.bitwise_and(o, self)
+    def __or__(self, o): return np.bitwise_or(self, o)
+    def __ror__(self, o): return np.bitwise_or(o, self)
+    def __xor__(self, o): return np.bitwise_xor(self, o)
+    def __rxor__(self, o): return np.bitwise_xor(o, self)
+    def __invert__(self): return np.invert(self)
 
     @property
     def T(self):

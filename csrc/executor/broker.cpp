@@ -68,6 +68,14 @@ class HipDevice final : public broker::Device {
     int (*gemm_fp)(int, int, int, const void*, const void*, void*, int, int, int, int64_t, int64_t, int64_t, hipStream_t);
     int (*gemm_f32x6)(int, int, const void*, const void*, void*, int, int, int, int64_t, int64_t, int64_t, void*, int64_t,
                       hipStream_t);
+    // boolean masks (csrc/kernels/mask.hip)
+    int (*compare)(int, int, int, const void*, const void*, double, void*, int64_t, hipStream_t);
+    int (*compare_count)(int, int, int, const void*, const void*, double, int64_t, void*, void*, hipStream_t);
+    int (*mask_logical)(int, const void*, const void*, void*, int64_t, hipStream_t);
+    int (*where)(int, const void*, int, const void*, const void*, double, double, void*, int64_t, hipStream_t);
+    int64_t (*compress_ws)();
+    int (*compress_ws_init)(void*, hipStream_t);
+    int (*compress)(int, const void*, const void*, int64_t, void*, int64_t, void*, hipStream_t);
   } bk{};
 
   // Per-session GPU resources, pooled across sessions: a stream, the
@@ -83,6 +91,7 @@ class HipDevice final : public broker::Device {
     void* scalar = nullptr;  // device fallback when no pinned slot exists
     double* slot = nullptr;
     void* axis_ws = nullptr;  // axis-reduction partials, allocated on first use
+    void* compress_ws = nullptr;  // compaction counts and offsets, allocated on first use
     // frees waiting for the stream work recorded before them (event, buffer)
     std::vector<std::pair<hipEvent_t, void*>> pending;
     std::vector<hipEvent_t> spare_events;
@@ -300,6 +309,13 @@ class HipDevice final : public broker::Device {
     sym(lib_, "bk_gemm_bf16_nn", &bk.gemm_nn);
     sym(lib_, "bk_gemm_fp", &bk.gemm_fp);
     sym(lib_, "bk_gemm_f32x6", &bk.gemm_f32x6);
+    sym(lib_, "bk_compare", &bk.compare);
+    sym(lib_, "bk_compare_count", &bk.compare_count);
+    sym(lib_, "bk_mask_logical", &bk.mask_logical);
+    sym(lib_, "bk_where", &bk.where);
+    if (!sym(lib_, "bk_compress_workspace_bytes", &bk.compress_ws) ||
+        !sym(lib_, "bk_compress_workspace_init", &bk.compress_ws_init) || !sym(lib_, "bk_compress", &bk.compress))
+      bk.compress = nullptr;
     return true;
   }
 
@@ -547,6 +563,44 @@ class HipDevice final : public broker::Device {
     // ~10 us -- short next to the GEMM that produced it
     return timed(s, pick(s, short_bytes(rows * ld, elem_bytes(dt)) || rows * ld <= (16ll << 20)),
                  [&](hipStream_t q) { return bk.reduce_axis((int)op, (int)dt, x, rows, cols, ld, (int)axis, y, c->axis_ws, q); });
+  }
+  // boolean masks: a mask is one byte per element
+  int compare(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double sc, void* y, int64_t n,
+              void* s) override {
+    if (!bk.compare) return broker::kBadArgument;
+    return timed(s, pick(s, short_bytes(n, elem_bytes(dt) * (mode == 0 ? 2 : 1) + 1)),
+                 [&](hipStream_t q) { return bk.compare((int)op, (int)dt, (int)mode, a, b, sc, y, n, q); });
+  }
+  int compare_count(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double sc, int64_t n,
+                    double* out, void* s) override {
+    if (!bk.compare_count) return broker::kBadArgument;
+    Ctx* c = (Ctx*)s;
+    const int rc = timed(s, pick(s, short_bytes(n, elem_bytes(dt), mode == 0 ? 2 : 1)), [&](hipStream_t q) {
+      return bk.compare_count((int)op, (int)dt, (int)mode, a, b, sc, n, c->ws, c->slot ? (void*)c->slot : c->scalar, q);
+    });
+    return fetch(c, rc, out);
+  }
+  int mask_logical(uint32_t op, const void* a, const void* b, void* y, int64_t n, void* s) override {
+    if (!bk.mask_logical) return broker::kBadArgument;
+    return timed(s, pick(s, short_bytes(n, 1, 3)),
+                 [&](hipStream_t q) { return bk.mask_logical((int)op, a, b, y, n, q); });
+  }
+  int where(uint32_t dt, const void* m, uint32_t flags, const void* a, const void* b, double sa, double sb, void* y,
+            int64_t n, void* s) override {
+    if (!bk.where) return broker::kBadArgument;
+    return timed(s, pick(s, short_bytes(n, elem_bytes(dt) * 3 + 1)),
+                 [&](hipStream_t q) { return bk.where((int)dt, m, (int)flags, a, b, sa, sb, y, n, q); });
+  }
+  int compress(uint32_t dt, const void* x, const void* m, int64_t n, void* y, int64_t cap, void* s) override {
+    Ctx* c = (Ctx*)s;
+    if (!bk.compress) return broker::kBadArgument;
+    if (!c->compress_ws) {
+      if (bk.malloc_(&c->compress_ws, bk.compress_ws()) != 0) return broker::kOutOfMemory;
+      bk.compress_ws_init(c->compress_ws, c->s);
+    }
+    const int64_t es = dt == broker::kDtBool ? 1 : elem_bytes(dt);
+    return timed(s, pick(s, short_bytes(n, 2 * es + 2)),
+                 [&](hipStream_t q) { return bk.compress((int)dt, x, m, n, y, cap, c->compress_ws, q); });
   }
   const char* last_error() override { return bk.last_error ? bk.last_error() : ""; }
   void info(int64_t v[5]) override {

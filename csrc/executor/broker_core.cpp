@@ -15,7 +15,8 @@ const char* op_name(uint32_t op) {
                                       "bk.read",     "bk.rand",  "bk.unary",  "bk.binary",    "bk.cast",
                                       "bk.fill",     "bk.reduce", "bk.gemm",  "bk.transpose", "bk.sync",
                                       "bk.memstats", "bk.info",  "bk.copy",   "bk.rand_reduce", "bk.alloc_at",
-                                      "bk.reduce_axis", "bk.gemm_fp"};
+                                      "bk.reduce_axis", "bk.gemm_fp", "bk.compare", "bk.compare_count",
+                                      "bk.mask_logical", "bk.where", "bk.compress"};
   return op < sizeof(names) / sizeof(names[0]) ? names[op] : names[0];
 }
 
@@ -306,9 +307,12 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
       const int64_t n = r.get<int64_t>();
       if (!r.ok) return kProtocol;
       const bool two = rop == 5 || rop == 6;  // dot and max|a-b| read b
+      // a mask (n bytes): count, any, all only
+      const bool mask = dt == kDtBool;
+      const uint64_t esize = mask ? (rop == 0 || rop == 3 || rop == 4 ? 1 : 0) : (uint64_t)dtype_size(dt);
       uint64_t need;
       Buf *ba = lookup(a), *bb = two ? lookup(bh) : nullptr;
-      if (n < 0 || !dtype_size(dt) || !mul_ok((uint64_t)n, dtype_size(dt), &need) || !ba || need > ba->size ||
+      if (n < 0 || !esize || !mul_ok((uint64_t)n, esize, &need) || !ba || need > ba->size ||
           (two && (!bb || need > bb->size)))
         return kBadHandle;
       if (!will_read(ba) || !will_read(bb)) return kLaunchFailed;
@@ -407,6 +411,82 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
         return kBadHandle;
       if (!will_read(bx) || !will_write(by, 0, ny)) return kLaunchFailed;
       return dev_.reduce_axis(rop, dt, bx->ptr, by->ptr, rows, cols, ld, axis, stream_);
+    }
+    case kCompare:
+    case kCompareCount: {
+      const uint32_t cop = r.get<uint32_t>(), dt = r.get<uint32_t>(), mode = r.get<uint32_t>();
+      r.get<uint32_t>();
+      const uint64_t a = r.get<uint64_t>(), bh = r.get<uint64_t>();
+      const double sc = r.get<double>();
+      const uint64_t y = op == kCompare ? r.get<uint64_t>() : 0;
+      const int64_t n = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      uint64_t need;
+      Buf *ba = lookup(a), *bb = mode == 0 ? lookup(bh) : nullptr, *by = op == kCompare ? lookup(y) : nullptr;
+      if (n < 0 || cop > 5 || mode > 1 || dt > 2 || !mul_ok((uint64_t)n, dtype_size(dt), &need) || !ba ||
+          need > ba->size || (mode == 0 && (!bb || need > bb->size)))
+        return kBadHandle;
+      if (op == kCompareCount) {
+        if (!will_read(ba) || !will_read(bb)) return kLaunchFailed;
+        double v = 0;
+        const int rc = dev_.compare_count(cop, dt, mode, ba->ptr, bb ? bb->ptr : nullptr, sc, n, &v, stream_);
+        put(out, v);
+        return rc;
+      }
+      // the mask is n bytes, written while other lanes still read a and b: its own buffer
+      if (!by || (uint64_t)n > by->size || by == ba || by == bb) return kBadHandle;
+      if (!will_read(ba) || !will_read(bb) || !will_write(by, 0, (uint64_t)n)) return kLaunchFailed;
+      return dev_.compare(cop, dt, mode, ba->ptr, bb ? bb->ptr : nullptr, sc, by->ptr, n, stream_);
+    }
+    case kMaskLogical: {
+      const uint32_t lop = r.get<uint32_t>();
+      r.get<uint32_t>();
+      const uint64_t a = r.get<uint64_t>(), bh = r.get<uint64_t>(), y = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      const bool two = lop < 3;
+      Buf *ba = lookup(a), *bb = two ? lookup(bh) : nullptr, *by = lookup(y);
+      if (n < 0 || lop > 3 || !ba || !by || (uint64_t)n > ba->size || (uint64_t)n > by->size ||
+          (two && (!bb || (uint64_t)n > bb->size)))
+        return kBadHandle;
+      if (!will_read(ba) || !will_read(bb) || !will_write(by, 0, (uint64_t)n)) return kLaunchFailed;
+      return dev_.mask_logical(lop, ba->ptr, bb ? bb->ptr : nullptr, by->ptr, n, stream_);
+    }
+    case kWhere: {
+      const uint32_t dt = r.get<uint32_t>(), wflags = r.get<uint32_t>();
+      const uint64_t m = r.get<uint64_t>(), a = r.get<uint64_t>(), bh = r.get<uint64_t>();
+      const double sa = r.get<double>(), sb = r.get<double>();
+      const uint64_t y = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      const bool a_arr = !(wflags & 1), b_arr = !(wflags & 2);
+      uint64_t need;
+      Buf *bm = lookup(m), *ba = a_arr ? lookup(a) : nullptr, *bb = b_arr ? lookup(bh) : nullptr, *by = lookup(y);
+      if (n < 0 || (wflags & ~3u) != 0 || dt > 2 || !mul_ok((uint64_t)n, dtype_size(dt), &need) || !bm || !by ||
+          (uint64_t)n > bm->size || need > by->size || (a_arr && (!ba || need > ba->size)) ||
+          (b_arr && (!bb || need > bb->size)) || by == bm)
+        return kBadHandle;
+      if (!will_read(bm) || !will_read(ba) || !will_read(bb) || !will_write(by, 0, need)) return kLaunchFailed;
+      return dev_.where(dt, bm->ptr, wflags, ba ? ba->ptr : nullptr, bb ? bb->ptr : nullptr, sa, sb, by->ptr, n,
+                        stream_);
+    }
+    case kCompress: {
+      const uint32_t dt = r.get<uint32_t>();
+      r.get<uint32_t>();
+      const uint64_t x = r.get<uint64_t>(), m = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      const uint64_t y = r.get<uint64_t>();
+      const int64_t cap = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      const uint64_t esize = dt == kDtBool ? 1 : dt <= 2 ? (uint64_t)dtype_size(dt) : 0;
+      uint64_t need, room;
+      Buf *bx = lookup(x), *bm = lookup(m), *by = lookup(y);
+      if (n < 0 || cap < 0 || !esize || !mul_ok((uint64_t)n, esize, &need) || !mul_ok((uint64_t)cap, esize, &room) ||
+          !bx || !bm || !by || need > bx->size || (uint64_t)n > bm->size || room > by->size || by == bx || by == bm)
+        return kBadHandle;
+      // the output is written up to the mask's count only: scrubbed first, like a read
+      if (!will_read(bx) || !will_read(bm) || !will_read(by)) return kLaunchFailed;
+      return dev_.compress(dt, bx->ptr, bm->ptr, n, by->ptr, cap, stream_);
     }
     case kCopy: {
       const uint64_t d = r.get<uint64_t>(), doff = r.get<uint64_t>(), s = r.get<uint64_t>(), soff = r.get<uint64_t>(),

@@ -26,8 +26,23 @@ namespace broker {
 enum Op : uint32_t {
   kHello = 1, kAlloc, kFree, kWrite, kRead, kRand, kUnary, kBinary, kCast, kFill, kReduce, kGemm, kTranspose,
   kSync, kMemStats, kInfo, kCopy, kRandReduce, kAllocAt, kReduceAxis, kGemmFp,
+  // boolean masks (csrc/kernels/mask.hip): one byte per element, so a mask of n
+  // elements needs n bytes; float operands (dt 0 f32, 1 f64, 2 bf16) n * size.
+  //   kCompare      u32 op | u32 dt | u32 mode | u32 0 | u64 a | u64 b | f64 scalar | u64 mask_out | i64 n
+  //                 op 0 < 1 <= 2 > 3 >= 4 == 5 !=; mode 0 array-array, 1 array-scalar (b ignored);
+  //                 mask_out is another buffer than a and b
+  //   kCompareCount u32 op | u32 dt | u32 mode | u32 0 | u64 a | u64 b | f64 scalar | i64 n
+  //                 replies one f64 (the number of true comparisons), like kReduce
+  //   kMaskLogical  u32 op | u32 0 | u64 a | u64 b | u64 out | i64 n      op 0 and, 1 or, 2 xor, 3 not (b ignored)
+  //   kWhere        u32 dt | u32 flags | u64 mask | u64 a | u64 b | f64 sa | f64 sb | u64 out | i64 n
+  //                 flags bit 0: A is the scalar sa (a ignored), bit 1: B is the scalar sb (b ignored)
+  //   kCompress     u32 dt | u32 0 | u64 x | u64 mask | i64 n | u64 out | i64 cap
+  //                 dt 0 / 1 / 2 or 6 (bool); out holds cap elements and is another buffer than x and mask
+  // kReduce also takes dt 6 (a mask of n bytes) with op 0 (count), 3 (any), 4 (all).
+  kCompare, kCompareCount, kMaskLogical, kWhere, kCompress,
   kOpCount
 };
+constexpr uint32_t kDtBool = 6;  // not a dtype_size() code: the mask ops size masks as n bytes themselves
 enum Status : int32_t {
   kOk = 0, kBadArgument = 1, kLaunchFailed = 2, kOutOfMemory = 3, kQuotaExceeded = 4, kNotInitialized = 5,
   kBadHandle = 6, kProtocol = 7,
@@ -114,6 +129,21 @@ class Device {
                          uint64_t, void*) {
     return kBadArgument;
   }
+  // boolean masks (bk_compare, bk_compare_count, bk_mask_logical, bk_where,
+  // bk_compress); kBadArgument where the device has no such kernel.
+  // compare_count is synchronous like reduce: the count lands in *out
+  virtual int compare(uint32_t, uint32_t, uint32_t, const void*, const void*, double, void*, int64_t, void*) {
+    return kBadArgument;
+  }
+  virtual int compare_count(uint32_t, uint32_t, uint32_t, const void*, const void*, double, int64_t, double*, void*) {
+    return kBadArgument;
+  }
+  virtual int mask_logical(uint32_t, const void*, const void*, void*, int64_t, void*) { return kBadArgument; }
+  virtual int where(uint32_t, const void*, uint32_t, const void*, const void*, double, double, void*, int64_t, void*) {
+    return kBadArgument;
+  }
+  // out[0 : min(count, cap)] = x[mask]; nothing at or past index cap is written
+  virtual int compress(uint32_t, const void*, const void*, int64_t, void*, int64_t, void*) { return kBadArgument; }
   virtual int transpose(int sdt, int ddt, const void* in, void* out, int rows, int cols, int ldi, int ldo, void* s) = 0;
   // per-column (axis 0) / per-row (axis 1) sum or mean into y (f64 for f64 x, else f32)
   virtual int reduce_axis(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,

@@ -98,8 +98,51 @@ class HostDevice final : public Device {
     return 0;
   }
   int reduce(uint32_t op, uint32_t dt, const void* a, const void* b, int64_t n, double* out, void*) override {
+    if (dt == kDtBool) {  // a mask of n bytes: count, any, all
+      if (op != 0 && op != 3 && op != 4) return kBadArgument;
+      *out = sum(a, (uint64_t)n);
+      return 0;
+    }
     if (op > 6 || dt > 2 || ((op == 5 || op == 6) && !b)) return kBadArgument;
     *out = sum(a, (uint64_t)n * dtype_size(dt)) + (b ? sum(b, (uint64_t)n * dtype_size(dt)) : 0);
+    return 0;
+  }
+  // the mask ops: n * size bytes of every float operand, n of every mask,
+  // cap * size of a compress output
+  int compare(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double, void* y, int64_t n,
+              void*) override {
+    if (op > 5 || dt > 2 || mode > 1 || (mode == 0 && !b)) return kBadArgument;
+    const double v = sum(a, (uint64_t)n * dtype_size(dt)) + (mode == 0 ? sum(b, (uint64_t)n * dtype_size(dt)) : 0);
+    touch_w(y, (uint64_t)n, v > 0 ? 1 : 0);
+    return 0;
+  }
+  int compare_count(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double, int64_t n,
+                    double* out, void*) override {
+    if (op > 5 || dt > 2 || mode > 1 || (mode == 0 && !b)) return kBadArgument;
+    *out = sum(a, (uint64_t)n * dtype_size(dt)) + (mode == 0 ? sum(b, (uint64_t)n * dtype_size(dt)) : 0);
+    return 0;
+  }
+  int mask_logical(uint32_t op, const void* a, const void* b, void* y, int64_t n, void*) override {
+    if (op > 3 || (op < 3 && !b)) return kBadArgument;
+    if (op < 3) sum(b, (uint64_t)n);
+    copy(y, a, (uint64_t)n);
+    return 0;
+  }
+  int where(uint32_t dt, const void* m, uint32_t flags, const void* a, const void* b, double, double, void* y,
+            int64_t n, void*) override {
+    if (dt > 2 || (flags & ~3u) || (!(flags & 1) && !a) || (!(flags & 2) && !b)) return kBadArgument;
+    const uint64_t nb = (uint64_t)n * dtype_size(dt);
+    double v = sum(m, (uint64_t)n);
+    if (!(flags & 1)) v += sum(a, nb);
+    if (!(flags & 2)) v += sum(b, nb);
+    touch_w(y, nb, v > 0 ? 1 : 0);
+    return 0;
+  }
+  int compress(uint32_t dt, const void* x, const void* m, int64_t n, void* y, int64_t cap, void*) override {
+    const uint64_t es = dt == kDtBool ? 1 : dt <= 2 ? (uint64_t)dtype_size(dt) : 0;
+    if (!es || cap < 0) return kBadArgument;
+    const double v = sum(x, (uint64_t)n * es) + sum(m, (uint64_t)n);
+    touch_w(y, (uint64_t)cap * es, v > 0 ? 1 : 0);  // (the most the kernel may write: a mask of at least cap trues)
     return 0;
   }
   int rand_reduce(uint32_t op, uint32_t dt, int64_t n, uint64_t, uint64_t, double, double, double* out, void*) override {

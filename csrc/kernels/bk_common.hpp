@@ -32,10 +32,13 @@ enum Status : int {
   kNotInitialized = 5,
 };
 
-enum DType : int { kF32 = 0, kF64 = 1, kBF16 = 2, kF16 = 3, kI32 = 4, kI64 = 5 };
+// kBool: numpy's bool, one byte per element -- kernels write exactly 0 or 1
+// and read any non-zero byte as true (mask.hip)
+enum DType : int { kF32 = 0, kF64 = 1, kBF16 = 2, kF16 = 3, kI32 = 4, kI64 = 5, kBool = 6 };
 
 inline int dtype_size(int dt) {
   switch (dt) {
+    case kBool: return 1;
     case kF32: case kI32: return 4;
     case kF64: case kI64: return 8;
     case kBF16: case kF16: return 2;

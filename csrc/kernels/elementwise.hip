@@ -1,4 +1,4 @@
-// Elementwise kernels (square, unary math, binary arithmetic, casts).
+// Elementwise kernels (square, unary math, binary arithmetic, casts, bool -> float).
 //
 // HBM-bound: every lane moves 16 bytes per access (f64x2 / f32x4 / bf16x8,
 // Guideline 13), non-temporal for arrays past the Infinity Cache
@@ -167,6 +167,26 @@ __global__ __launch_bounds__(256) void cast_kernel(const TI* __restrict__ x, TO*
   }
 }
 
+// kBool -> f32 / f64: any non-zero byte is 1.0 (16 mask bytes per lane and load)
+template <typename TO>
+__global__ __launch_bounds__(256) void bool_cast_kernel(const uint8_t* __restrict__ x, TO* __restrict__ y, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nvec = n / 16;
+  for (int64_t i = tid; i < nvec; i += stride) {
+    const Vec<uint8_t> m = reinterpret_cast<const Vec<uint8_t>*>(x)[i];
+    constexpr int N = Vec<TO>::N;
+#pragma unroll
+    for (int q = 0; q < 16 / N; ++q) {
+      Vec<TO> o;
+#pragma unroll
+      for (int j = 0; j < N; ++j) o.v[j] = m.v[q * N + j] != 0 ? TO(1) : TO(0);
+      reinterpret_cast<Vec<TO>*>(y)[i * (16 / N) + q] = o;
+    }
+  }
+  for (int64_t k = nvec * 16 + tid; k < n; k += stride) y[k] = x[k] != 0 ? TO(1) : TO(0);
+}
+
 __global__ __launch_bounds__(256) void fill_kernel(uint8_t* __restrict__ y, int64_t nbytes, uint64_t pattern,
                                                    int pattern_bytes) {
   // pattern_bytes in {1,2,4,8}; 16-B stores for the bulk.
@@ -256,6 +276,12 @@ BK_API int bk_binary(int op, int dtype, int mode, const void* a, const void* b, 
 BK_API int bk_cast(int src_dtype, int dst_dtype, const void* x, void* y, int64_t n, hipStream_t stream) {
   if (!x || !y || n < 0) return kBadArgument;
   if (n == 0) return kOk;
+  if (src_dtype == kBool && (dst_dtype == kF32 || dst_dtype == kF64)) {
+    const unsigned gb = stream_grid((n + 15) / 16, 256);
+    if (dst_dtype == kF32) bool_cast_kernel<float><<<gb, 256, 0, stream>>>((const uint8_t*)x, (float*)y, n);
+    else bool_cast_kernel<double><<<gb, 256, 0, stream>>>((const uint8_t*)x, (double*)y, n);
+    return launch_status();
+  }
   const unsigned g = stream_grid(n, 256);
 #define BK_CAST(TI, TO) cast_kernel<TI, TO><<<g, 256, 0, stream>>>((const TI*)x, (TO*)y, n)
   if (src_dtype == kF32 && dst_dtype == kBF16) BK_CAST(float, uint16_t);

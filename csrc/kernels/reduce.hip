@@ -16,14 +16,7 @@
 
 #include "bk_common.hpp"
 #include "bk_philox.hpp"
-
-// The completion-ticket fold below relies on GFX9-family memory semantics:
-// vmcnt counts stores and sc1 (agent-scope) accesses are coherent across
-// XCDs.  gfx10+ counts stores in vscnt, so the fold could read partials that
-// have not landed -- refuse to build for anything but gfx9 (gfx950 here).
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#error "reduce.hip: the single-pass ticket fold is written for GFX9-family (gfx950) memory semantics"
-#endif
+#include "bk_ticket.hpp"  // kRedBlock, kRedMaxBlocks and the completion tickets
 
 namespace bk {
 
@@ -32,13 +25,11 @@ namespace bk {
 enum ReduceOp : int { kRedSum = 0, kRedSquareSum, kRedAbsSum, kRedMax, kRedMin, kRedDot, kRedMaxAbsDiff, kRedCount };
 template <int OP> constexpr bool kTwoOperands = OP == kRedDot || OP == kRedMaxAbsDiff;
 
-constexpr int kRedBlock = 256;
-// stage-1 grid cap, and the workspace length: 32 blocks per CU with 16 loads
-// in flight per lane (tools/probe/reduce_probe.hip: 1e8 f64 square-sum
-// 152 -> 120 us, 5.2 -> 6.6 TB/s, with non-temporal loads)
-// (the workspace holds kRedMaxBlocks partials; the default grid is
-// kRedBlocks, BK_REDUCE_BLOCKS overrides it up to the workspace for sweeps)
-constexpr int kRedMaxBlocks = 32768;
+// kRedMaxBlocks (bk_ticket.hpp) is the stage-1 grid cap and the workspace
+// length: 32 blocks per CU with 16 loads in flight per lane
+// (tools/probe/reduce_probe.hip: 1e8 f64 square-sum 152 -> 120 us, 5.2 ->
+// 6.6 TB/s, with non-temporal loads); the default grid is kRedBlocks,
+// BK_REDUCE_BLOCKS overrides it up to the workspace for sweeps.
 // 512 blocks (2 per CU, 8 waves, 16 x 16-B loads in flight per lane):
 // tools/reduce_sweep.py on MI355X, 1e8 f64 square-sum, median of 20 --
 // grid-stride layout 167 / 135 / 141 / 154 / 164 / 178 us at 256 / 512 / 768 /
@@ -116,39 +107,7 @@ template <int OP> __device__ __forceinline__ double block_reduce(double v) {
 
 template <typename T> struct alignas(16) V16 { T v[16 / sizeof(T)]; };
 
-// ---- single-launch completion ------------------------------------------------
-// Every block publishes its partial, then takes a ticket; the block holding
-// the last ticket folds the partials and re-arms the ticket for the next
-// launch on this workspace.  Tickets start at zero (bk_reduce_workspace_init).
-//
-// Blocks sit on different XCDs, each with its own L2.  Partials are written
-// and read with agent-scope (sc1) accesses, which are coherent across XCDs;
-// a store is complete (vmcnt: GFX9 counts stores there) before its block's
-// ticket.  No release/acquire fences: at agent scope those write back and
-// invalidate the whole L2 (buffer_wbl2 / buffer_inv), per block -- what the
-// first version of this did cost every reduction ~1 ms under concurrent
-// sandboxes.
-__device__ __forceinline__ void publish(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ bool take_last_ticket(unsigned* ticket, unsigned count) {
-  __shared__ bool last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's partial stores have landed
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = prev == count - 1;
-  }
-  __syncthreads();
-  return last;
-}
-__device__ __forceinline__ double load_agent(const double* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void rearm(unsigned* ticket) {
-  __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
+// ---- single-launch completion (the tickets: bk_ticket.hpp) ----------------------
 // the fold of `count` partials into *out by the last block
 template <int OP>
 __device__ __forceinline__ void finish(double v, double* partials, unsigned* ticket, double* out) {
@@ -507,6 +466,9 @@ int launch_reduce(const void* a, const void* b, int64_t n, double* workspace, do
   return launch_status();
 }
 
+// bk_reduce on a kBool mask: op 0 the count of non-zero bytes, 3 any, 4 all (mask.hip)
+int reduce_bool(int op, const void* a, int64_t n, void* workspace, void* out, hipStream_t stream);
+
 template <typename T, int... OPS>
 int dispatch_reduce(int op, const void* a, const void* b, int64_t n, double* ws, double* out, hipStream_t s,
                     std::integer_sequence<int, OPS...>) {
@@ -775,6 +737,7 @@ BK_API int bk_reduce(int op, int dtype, const void* a, const void* b, int64_t n,
     case kF64: return dispatch_reduce<double>(op, a, b, n, (double*)workspace, (double*)out, stream, Ops{});
     case kF32: return dispatch_reduce<float>(op, a, b, n, (double*)workspace, (double*)out, stream, Ops{});
     case kBF16: return dispatch_reduce<uint16_t>(op, a, b, n, (double*)workspace, (double*)out, stream, Ops{});
+    case kBool: return reduce_bool(op, a, n, workspace, out, stream);  // count / any / all (mask.hip)
   }
   return kBadArgument;
 }

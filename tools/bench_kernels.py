@@ -44,6 +44,82 @@ def torch_timed(fn, reps=20, warmup=3):
     return statistics.median(times), min(times)
 
 
+def spread(fn, timer, reps=20, warmup=3):
+    """median, min and max of `reps` timed calls (timer: timed / torch_timed's loop)."""
+    for _ in range(warmup):
+        fn()
+    bk.synchronize()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        if timer == "bk":
+            with bk.Timer() as t:
+                fn()
+            times.append(t.ms)
+        else:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            fn()
+            e.record()
+            e.synchronize()
+            times.append(s.elapsed_time(e))
+    return statistics.median(times), min(times), max(times)
+
+
+def mask_rows():
+    """The mask kernels (csrc/kernels/mask.hip) against torch eager, n = 1e8
+    f64 random data: `python tools/bench_kernels.py masks`
+    (profiles/mask_kernels.jsonl).  The fused compare-count reads the bytes
+    bk.sum reads with the same stream shape: it is also set against bk.sum
+    of the same array in the same run."""
+    from bee_code_interpreter_fs_amd.ops.array import driver
+
+    bk.init()
+    emit(kernel="device", **bk.device_info())
+    n = 10**8
+    x = bk.random.rand(n)._materialize()
+    y = bk.random.rand(n)._materialize()
+    tx = torch.empty(n, dtype=torch.float64, device="cuda").uniform_()
+    ty = torch.empty(n, dtype=torch.float64, device="cuda").uniform_()
+
+    def row(kernel, fn, timer, nbytes, **kw):
+        ms, mn, mx = spread(fn, timer)
+        emit(kernel=kernel, n=n, ms=ms, min_ms=mn, max_ms=mx, GBps=nbytes / ms / 1e6, **kw)
+        return ms, mn, mx
+
+    row("compare_le f64 (array <= 0.5 -> mask)", lambda: bk.less_equal(x, 0.5)._materialize(), "bk", n * 9)
+    row("torch.le f64", lambda: torch.le(tx, 0.5), "torch", n * 9)
+    row("compare_le f64 (array <= array -> mask)", lambda: bk.less_equal(x, y)._materialize(), "bk", n * 17)
+    row("torch.le f64 (array, array)", lambda: torch.le(tx, ty), "torch", n * 17)
+
+    s_ms, s_mn, s_mx = row("sum_f64 (incl. 8B readback)", lambda: bk.sum(x), "bk", n * 8)
+    c_ms, _, _ = row("compare_count f64 fused (x <= 0.5, incl. 8B readback)",
+                     lambda: bk.count_nonzero(bk.less_equal(x, 0.5)), "bk", n * 8)
+    emit(kernel="compare_count vs sum_f64", ratio=c_ms / s_ms, inside_sum_spread=bool(s_mn <= c_ms <= s_mx))
+    # the same two at the driver: the timed span of the rows above starts
+    # before the Python that builds the lazy mask, these hold the launch only
+    drv = driver()
+    s_ms, s_mn, s_mx = row("sum_f64 (driver call, incl. 8B readback)", lambda: drv.reduce(0, x.code, x.ptr, 0, n),
+                           "bk", n * 8)
+    c_ms, _, _ = row("compare_count f64 fused (driver call, incl. 8B readback)",
+                     lambda: drv.compare_count(1, x.code, 1, x.ptr, 0, 0.5, n), "bk", n * 8)
+    emit(kernel="compare_count vs sum_f64 (driver calls)", ratio=c_ms / s_ms,
+         inside_sum_spread=bool(s_mn <= c_ms <= s_mx))
+    row("torch.count_nonzero(tx <= 0.5) f64", lambda: torch.count_nonzero(tx <= 0.5).item(), "torch", n * 8)
+
+    m = bk.less_equal(x, 0.5)._materialize()
+    tm = tx <= 0.5
+    row("where f64 (mask, array, array)", lambda: bk.where(m, x, y), "bk", n * 25)
+    row("torch.where f64", lambda: torch.where(tm, tx, ty), "torch", n * 25)
+
+    count = bk.count_nonzero(m)
+    row("compress f64, 50% (x[mask]: count + 2 launches)", lambda: x[m], "bk", n * 10 + count * 8, density=count / n)
+    out = bk.empty(count, "float64")
+    row("compress f64, 50% (kernels only, count known)",
+        lambda: drv.compress(x.code, x.ptr, m.ptr, n, out.ptr, count), "bk", n * 10 + count * 8)
+    row("torch tx[tm] f64, 50%", lambda: tx[tm], "torch", n * 10 + count * 8)
+
+
 def emit(**kw):
     print(json.dumps(kw), flush=True)
 
@@ -129,4 +205,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    mask_rows() if sys.argv[1:] == ["masks"] else main()
