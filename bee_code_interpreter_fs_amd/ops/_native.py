@@ -106,6 +106,13 @@ def _declare(lib: ctypes.CDLL) -> None:
         "bk_compress_workspace_bytes": ([], c_i64),
         "bk_compress_workspace_init": ([c_vp, c_vp], c_int),
         "bk_compress": ([c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
+        "bk_select_workspace_bytes": ([], c_i64),
+        "bk_select_workspace_init": ([c_vp, c_vp], c_int),
+        "bk_select": ([c_int, c_vp, c_i64, ctypes.POINTER(c_i64), c_int, c_vp, c_vp, c_vp], c_int),
+        "bk_histogram_max_bins": ([], c_int),
+        "bk_histogram_workspace_bytes": ([], c_i64),
+        "bk_histogram_workspace_init": ([c_vp, c_vp], c_int),
+        "bk_histogram": ([c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp], c_int),
         "bk_reduce_axis_workspace_bytes": ([], c_i64),
         "bk_reduce_workspace_init": ([c_vp, c_vp], c_int),
         "bk_reduce_axis_workspace_init": ([c_vp, c_vp], c_int),

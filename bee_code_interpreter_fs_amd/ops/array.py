@@ -14,6 +14,11 @@ byte per element as numpy's; a mask is *lazy* too: ``sum`` / ``mean`` /
 operands (no mask written), any other use (``where``, ``x[mask]``, ``&``)
 materialises it.
 
+``median`` / ``percentile`` / ``quantile`` / ``histogram`` summarise a whole
+array without sorting or copying it (``csrc/kernels/stats.hip``: a radix
+select of a few ranks, a histogram counted in LDS); they read a ``.T`` view in
+place and return host scalars / ndarrays typed as numpy's.
+
 ``square`` (and ``x * x`` / ``x ** 2``) returns a *lazy* array: if the only
 consumer is a reduction the square is fused into it (no 800 MB temporary);
 any other use materialises it with the elementwise kernel.
@@ -853,6 +858,137 @@ def where(mask, a, b, dtype=None) -> DeviceArray:
     driver().where(DTYPE_CODES[dt], mask.ptr, flags, a.ptr if not flags & 1 else 0, b.ptr if not flags & 2 else 0,
                    float(a) if flags & 1 else 0.0, float(b) if flags & 2 else 0.0, out.ptr, mask.size)
     return out
+
+
+# ---- order statistics and histograms (csrc/kernels/stats.hip) ------------------------
+
+_SELECT_Q = 16  # quantiles per select call: two neighbouring ranks each, 32 ranks a call
+MAX_HISTOGRAM_BINS = 4096  # = kMaxBins (stats.hip), driver.MAX_BINS
+
+
+def _stats_operand(what: str, x) -> DeviceArray:
+    """The array whose elements ``what`` looks at, in whatever order the
+    buffer holds them: a lazy draw gets its buffer, a ``.T`` view is read in
+    place (neither order statistics nor counts depend on element order)."""
+    x = _as_operand(x)
+    if x.dtype not in _FLOATS:
+        raise TypeError(f"beekern {what}: float arrays only, got {x.dtype}")
+    if x._lazy is not None:
+        x._materialize()
+    return x
+
+
+def _result_type(dtype: str):
+    return np.float64 if dtype == "float64" else np.float32  # (bf16 results are float32)
+
+
+def _lerp(a: float, b: float, g: float) -> float:
+    """a + (b - a) * g in f64, from whichever end is nearer as numpy's
+    quantile does (``_lerp``: b - (b - a) * (1 - g) for g >= 0.5)."""
+    d = b - a
+    return b - d * (1.0 - g) if g >= 0.5 else a + d * g
+
+
+def _quantiles(x: DeviceArray, qs: Sequence[float]) -> list:
+    """numpy's "linear" quantiles of the whole array, as f64 Python floats
+    (NaN for every one if x holds a NaN)."""
+    n = x.size
+    out: list = []
+    for i in range(0, len(qs), _SELECT_Q):
+        part = qs[i:i + _SELECT_Q]
+        ranks, gammas = [], []
+        for q in part:
+            virtual = (n - 1) * q
+            lo = min(max(int(math.floor(virtual)), 0), n - 1)
+            ranks += [lo, min(lo + 1, n - 1)]
+            gammas.append(virtual - lo)
+        values, nans = driver().select(x.code, x._buf.ptr, n, ranks)  # type: ignore[union-attr]
+        if nans:
+            return [math.nan] * len(qs)
+        out += [_lerp(values[2 * j], values[2 * j + 1], g) for j, g in enumerate(gammas)]
+    return out
+
+
+def _quantile(what: str, x, q, scale: float):
+    x = _stats_operand(what, x)
+    if x.size == 0:
+        raise ValueError(f"beekern {what}: the array is empty")
+    qa = np.asarray(q, dtype=np.float64)
+    if qa.ndim > 1:
+        raise ValueError(f"beekern {what}: q is a scalar or a 1-D sequence")
+    qs = [float(v) / scale for v in qa.reshape(-1)]
+    for v in qs:
+        if not 0.0 <= v <= 1.0:  # (a NaN too)
+            raise ValueError("Percentiles must be in the range [0, 100]" if scale == 100.0
+                             else "Quantiles must be in the range [0, 1]")
+    res = _quantiles(x, qs)
+    if qa.ndim == 0:
+        return _result_type(x.dtype)(res[0])
+    return np.array(res, np.float64)
+
+
+def percentile(x, q):
+    """np.percentile(x, q) of the whole array (method "linear"): a scalar of
+    the array's dtype for a scalar ``q`` (float32 for bf16), a host float64
+    ndarray for a 1-D sequence.  No sort: a radix select of the neighbouring
+    ranks, interpolated in f64 and rounded once."""
+    return _quantile("percentile", x, q, 100.0)
+
+
+def quantile(x, q):
+    """np.quantile(x, q) of the whole array; see :func:`percentile`."""
+    return _quantile("quantile", x, q, 1.0)
+
+
+def median(x):
+    """np.median(x) of the whole array: the middle element, or the mean of the
+    middle two in the array's dtype as numpy takes it; NaN if x holds one."""
+    x = _stats_operand("median", x)
+    n = x.size
+    if n == 0:
+        raise ValueError("beekern median: the array is empty")
+    rt = _result_type(x.dtype)
+    values, nans = driver().select(x.code, x._buf.ptr, n, [(n - 1) // 2, n // 2])  # type: ignore[union-attr]
+    if nans:
+        return rt(math.nan)
+    return np.mean(np.array(values if n % 2 == 0 else values[:1], rt))
+
+
+def histogram(x, bins=10, range=None, density=False):  # noqa: A002 - numpy's parameter name
+    """np.histogram(x, bins, range, density=density) of the whole array:
+    (counts, edges) as host ndarrays.  ``bins``: an int or a 1-D sequence of
+    edges, at most 4096 bins.  The edges are numpy's own
+    (``np.histogram_bin_edges`` on the array's [min, max] or ``range``, in the
+    array's dtype); the counts follow numpy's bin rule exactly."""
+    x = _stats_operand("histogram", x)
+    rt = _result_type(x.dtype)
+    if is_integer(bins):
+        if int(bins) > MAX_HISTOGRAM_BINS:
+            raise ValueError(f"beekern histogram: at most {MAX_HISTOGRAM_BINS} bins, got {int(bins)}")
+        if range is not None:
+            ends = np.array([range[0], range[1]], rt)  # (numpy looks at the data's dtype only)
+        elif x.size:
+            lo, hi = (driver().reduce(_REDUCE[op], x.code, x._buf.ptr, 0, x.size) for op in ("min", "max"))  # type: ignore[union-attr]
+            ends = np.array([lo, hi], rt)
+        else:
+            ends = np.array([], rt)
+        edges = np.histogram_bin_edges(ends, int(bins), range=range)  # (numpy's errors for a bad bins / range)
+    else:
+        if isinstance(bins, str):
+            raise TypeError("beekern histogram: bins is an int or a sequence of edges (no estimator names)")
+        edges = np.histogram_bin_edges(np.array([], rt), bins, range=range)
+        if edges.size - 1 > MAX_HISTOGRAM_BINS:
+            raise ValueError(f"beekern histogram: at most {MAX_HISTOGRAM_BINS} bins, got {edges.size - 1}")
+        if not np.isfinite(edges).all():
+            raise ValueError("beekern histogram: the edges must be finite")
+    if edges.size < 2 or x.size == 0:
+        counts = np.zeros(max(edges.size - 1, 0), np.int64)
+    else:
+        counts = driver().histogram(x.code, x._buf.ptr, x.size, edges.astype(np.float64))  # type: ignore[union-attr]
+    if density:
+        db = np.array(np.diff(edges), float)
+        return counts / db / counts.sum(), edges
+    return counts, edges
 
 
 # ---- matmul --------------------------------------------------------------------------

@@ -31,6 +31,15 @@ from ._native import BeekernError, QuotaExceeded, check
 _vp = ctypes.c_void_p
 
 
+# bk_select takes 1 to MAX_RANKS ranks a call, bk_histogram 1 to MAX_BINS bins
+# (kMaxRanks / kMaxBins of csrc/kernels/stats.hip and the broker's checks)
+MAX_RANKS = 32
+MAX_BINS = 4096
+_STATS_EDGES_AT = 512
+_STATS_COUNTS_AT = _STATS_EDGES_AT + (MAX_BINS + 1) * 8
+_STATS_SCRATCH_BYTES = _STATS_COUNTS_AT + MAX_BINS * 8
+
+
 class NativeDriver:
     name = "native"
 
@@ -42,6 +51,9 @@ class NativeDriver:
         self.scalar = 0
         self.axis_ws = 0
         self.compress_ws = 0
+        self.select_ws = 0
+        self.hist_ws = 0
+        self.stats_scratch = 0
 
     def init(self, device: int) -> None:
         check(self.lib.bk_init(int(device)), "bk_init")
@@ -157,6 +169,48 @@ class NativeDriver:
         check(self.lib.bk_compress(dt, _vp(x), _vp(mask), n, _vp(y), cap, _vp(self.compress_ws), self.stream),
               "bk_compress")
 
+    # ---- order statistics and histograms (csrc/kernels/stats.hip) ---------------------
+    def _stats_scratch(self) -> int:
+        """Device scratch of the two ops: 33 f64 select results, then the
+        histogram's edges (MAX_BINS + 1 f64) and counts (MAX_BINS u64)."""
+        if not self.stats_scratch:
+            self.stats_scratch = self.malloc(_STATS_SCRATCH_BYTES)
+        return self.stats_scratch
+
+    def select(self, dt: int, x: int, n: int, ranks) -> tuple:
+        """(np.sort(x)[k] as a float for every 0-based k of ``ranks`` (1 to
+        32 of them), the number of NaNs in x); x is only read."""
+        ranks = [int(k) for k in ranks]
+        if not self.select_ws:
+            self.select_ws = self.malloc(self.lib.bk_select_workspace_bytes())
+            check(self.lib.bk_select_workspace_init(_vp(self.select_ws), self.stream), "bk_select_workspace_init")
+        out = self._stats_scratch()
+        karr = (ctypes.c_int64 * max(len(ranks), 1))(*ranks)
+        check(self.lib.bk_select(dt, _vp(x), n, karr, len(ranks), _vp(out), _vp(self.select_ws), self.stream),
+              "bk_select")
+        host = np.zeros(len(ranks) + 1, np.float64)
+        self.d2h(out, host)
+        return [float(v) for v in host[:-1]], int(host[-1])
+
+    def histogram(self, dt: int, x: int, n: int, edges: np.ndarray) -> np.ndarray:
+        """int64 counts of np.histogram's bin rule for the ``len(edges) - 1``
+        bins between the non-decreasing f64 ``edges`` (at most MAX_BINS bins)."""
+        edges = np.ascontiguousarray(edges, np.float64)
+        bins = edges.size - 1
+        if not 1 <= bins <= MAX_BINS:
+            raise BeekernError(f"bk_histogram: 1 to {MAX_BINS} bins, got {bins}")
+        if not self.hist_ws:
+            self.hist_ws = self.malloc(self.lib.bk_histogram_workspace_bytes())
+            check(self.lib.bk_histogram_workspace_init(_vp(self.hist_ws), self.stream), "bk_histogram_workspace_init")
+        base = self._stats_scratch()
+        d_edges, d_counts = base + _STATS_EDGES_AT, base + _STATS_COUNTS_AT
+        self.h2d(d_edges, edges)
+        check(self.lib.bk_histogram(dt, _vp(x), n, _vp(d_edges), bins, _vp(d_counts), _vp(self.hist_ws), self.stream),
+              "bk_histogram")
+        counts = np.zeros(bins, np.uint64)
+        self.d2h(d_counts, counts)
+        return counts.astype(np.int64)
+
     def transpose(self, src: int, dst: int, rows: int, cols: int, ldi: int, ldo: int, src_dtype: int = 2,
                   dst_dtype: int = 2) -> None:
         check(self.lib.bk_transpose(src_dtype, dst_dtype, _vp(src), _vp(dst), rows, cols, ldi, ldo, self.stream),
@@ -216,7 +270,7 @@ def _info_dict(v, arch: str) -> dict:
 
 (HELLO, ALLOC, FREE, WRITE, READ, RAND, UNARY, BINARY, CAST, FILL, REDUCE, GEMM, TRANSPOSE, SYNC, MEMSTATS, INFO,
  COPY, RAND_REDUCE, ALLOC_AT, REDUCE_AXIS, GEMM_FP, COMPARE, COMPARE_COUNT, MASK_LOGICAL, WHERE,
- COMPRESS) = range(1, 27)
+ COMPRESS, SELECT, HISTOGRAM) = range(1, 29)
 _HDR = struct.Struct("<IIQ")
 _NO_REPLY = 1  # request flag: no response unless a later request collects an error
 _RHDR = struct.Struct("<iIQ")
@@ -473,6 +527,19 @@ class BrokerDriver:
 
     def compress(self, dt, x, mask, n, y, cap) -> None:
         self._post(COMPRESS, struct.pack("<IIQQqQq", dt, 0, x, mask, n, y, cap))
+
+    # order statistics and histograms: both reply, like REDUCE
+    def select(self, dt, x, n, ranks) -> tuple:
+        ranks = [int(k) for k in ranks]
+        payload = struct.pack(f"<IIQq{len(ranks)}q", dt, len(ranks), x, n, *ranks)
+        v = struct.unpack(f"<{len(ranks) + 1}d", self._call(SELECT, payload))
+        return list(v[:-1]), int(v[-1])
+
+    def histogram(self, dt, x, n, edges) -> np.ndarray:
+        edges = np.ascontiguousarray(edges, np.float64)
+        bins = edges.size - 1
+        body = self._call(HISTOGRAM, struct.pack("<IIQq", dt, max(bins, 0), x, n) + edges.tobytes())
+        return np.frombuffer(body, np.uint64).astype(np.int64)
 
     def transpose(self, src, dst, rows, cols, ldi, ldo, src_dtype=2, dst_dtype=2) -> None:
         self._post(TRANSPOSE, struct.pack("<QQiiiiii", src, dst, rows, cols, ldi, ldo, src_dtype, dst_dtype))

@@ -28,6 +28,15 @@ what numpy would (same dtype rules, same shape):
 * masks: ``sum`` (``np.int64``) / ``mean`` / ``count_nonzero`` (also of a
   float array: the fused ``!= 0`` count) / ``any`` / ``all`` of a whole
   array, and the three-argument ``where(mask, x, y)``;
+* order statistics and histograms of a whole f32 / f64 array (or axis 0 of a
+  1-D one): ``median``, ``percentile`` / ``quantile`` (method "linear", ``q``
+  a host scalar, list or ndarray) and ``histogram`` (int ``bins`` or host
+  edges, at most 4096 bins, ``range``, ``density``) -- a radix select of the
+  ranks a quantile needs and a histogram counted against numpy's own edges
+  (``csrc/kernels/stats.hip``), typed as numpy types them; ``out``,
+  ``overwrite_input=True``, ``keepdims=True``, ``weights``, other methods, an
+  axis of a 2-D array, string ``bins``, ``q`` out of range, bf16 / bool and
+  empty arrays go to numpy on the host;
 * ``matmul`` / ``dot`` / ``@`` of 1-D and 2-D operands: f32 / f64 on the
   full-precision MFMA GEMM in numpy's result dtype (``ops/array.py``
   ``matmul_fp``, ``csrc/kernels/gemm_fp.hip``; ``.T`` views read in place),
@@ -358,6 +367,90 @@ def array_function(b: Binding, func, types, args, kwargs):
 _NO = object()
 
 
+def _host_numbers(b: Binding, v, max_len: int):
+    """A host scalar, list / tuple or ndarray (0-D or 1-D, at most ``max_len``
+    long) of real numbers as a float64 ndarray, else None."""
+    if b.is_mine(v) or isinstance(v, (str, bytes, bool, np.bool_)):
+        return None
+    if not isinstance(v, (int, float, np.integer, np.floating, list, tuple, np.ndarray)):
+        return None
+    try:
+        a = np.asarray(v)
+    except Exception:
+        return None
+    if a.dtype.kind not in "iuf" or a.ndim > 1 or a.size > max_len or (a.ndim == 1 and isinstance(v, (list, tuple))
+                                                                        and len(v) != a.size):
+        return None
+    return a.astype(np.float64)
+
+
+def _try_quantile(b: Binding, A, name: str, args, kwargs):
+    """np.median / np.percentile / np.quantile of a whole f32 / f64 device
+    array, method "linear": numpy's value and type, or _NO."""
+    if name == "median":
+        got = _bind(name, args, kwargs, ("a", "axis", "out", "overwrite_input", "keepdims"))
+        allowed = {"a", "axis"}
+    else:
+        got = _bind(name, args, kwargs, ("a", "q", "axis", "out", "overwrite_input", "method", "keepdims"))
+        allowed = {"a", "q", "axis", "method"}
+    if got is None:
+        return _NO
+    if got.get("overwrite_input") is False:
+        del got["overwrite_input"]
+    if not _kw_only(got, allowed) or (_given(got.get("method")) and got["method"] != "linear"):
+        return _NO
+    x = b.dev(got["a"])
+    if x is None or x.dtype not in _FP or x.size == 0:
+        return _NO
+    axis = got.get("axis")
+    if _given(axis) and not (x.ndim == 1 and isinstance(axis, (int, np.integer)) and not isinstance(axis, bool)
+                             and axis in (0, -1)):
+        return _NO
+    if name == "median":
+        return _as_result_scalar(A.median(x), x.dtype)
+    if "q" not in got:
+        return _NO
+    q = _host_numbers(b, got["q"], 1 << 20)
+    top = 100.0 if name == "percentile" else 1.0
+    if q is None or not bool(np.all((q >= 0.0) & (q <= top))):  # (out of range, NaN: numpy's own error)
+        return _NO
+    res = A.percentile(x, q) if name == "percentile" else A.quantile(x, q)
+    # numpy's result dtype follows q too (a list of Python numbers is a strong
+    # float64 / int64 array, a Python scalar is weak): ask numpy, on one element
+    like = getattr(np, name)(np.zeros(1, np.dtype(x.dtype)), got["q"])
+    return like.dtype.type(res) if q.ndim == 0 else res.astype(like.dtype)
+
+
+def _try_histogram(b: Binding, A, args, kwargs):
+    """np.histogram of a whole f32 / f64 device array: (int64 counts -- or the
+    density -- and numpy's edges), host ndarrays, or _NO."""
+    got = _bind("histogram", args, kwargs, ("a", "bins", "range", "density", "weights"))
+    if got is None or not _kw_only(got, {"a", "bins", "range", "density"}):
+        return _NO
+    x = b.dev(got["a"])
+    if x is None or x.dtype not in _FP or x.size == 0:
+        return _NO
+    bins = got.get("bins", 10)
+    if isinstance(bins, (int, np.integer)) and not isinstance(bins, (bool, np.bool_)):
+        if not 1 <= int(bins) <= A.MAX_HISTOGRAM_BINS:
+            return _NO
+        bins = int(bins)
+    else:
+        e = _host_numbers(b, bins, A.MAX_HISTOGRAM_BINS + 1)
+        if e is None or e.ndim != 1 or e.size < 2 or not np.isfinite(e).all() or bool(np.any(e[:-1] > e[1:])):
+            return _NO
+    rng = got.get("range")
+    if rng is not None:
+        r = _host_numbers(b, rng, 2) if isinstance(rng, (list, tuple, np.ndarray)) else None
+        if r is None or r.shape != (2,) or not np.isfinite(r).all() or r[0] > r[1]:
+            return _NO
+        rng = (rng[0], rng[1])
+    density = got.get("density")
+    if density is not None and not isinstance(density, (bool, np.bool_)):
+        return _NO
+    return A.histogram(x, bins, range=rng, density=bool(density))
+
+
 def _try_function(b, A, name, mod, args, kwargs):
     if name in ("shape", "ndim", "size") and args and b.dev(args[0]) is not None and len(args) + len(kwargs) == 1:
         d = b.dev(args[0])
@@ -463,6 +556,10 @@ def _try_function(b, A, name, mod, args, kwargs):
             return b.box(A.where(cond, vals[0], vals[1], dtype=dtype))
         except (TypeError, ValueError):
             return _NO
+    if name in ("median", "percentile", "quantile"):
+        return _try_quantile(b, A, name, args, kwargs)
+    if name == "histogram":
+        return _try_histogram(b, A, args, kwargs)
     if name == "copy" and len(args) == 1 and not kwargs:
         x = b.dev(args[0])
         return _NO if x is None else b.box(x.copy())

@@ -33,6 +33,10 @@ What the user sees:
   ``np.where(mask, x, y)``, ``mask.astype(float)`` and ``x[mask]`` (the mask a
   device-resident bool OffloadArray of x's shape) stay on the device, so
   ``np.sum(x**2 + y**2 <= 1.0)`` counts in one fused pass;
+* summaries: ``np.median``, ``np.percentile`` / ``np.quantile`` (method
+  "linear") and ``np.histogram`` of a device-resident array run on the GPU (a
+  radix select, a histogram in LDS) and return numpy's scalars / ndarrays;
+  the array stays on the device (``examples/monte_carlo_var.py``);
 * semantics: the first operation without a GPU kernel (any other indexing, slicing,
   printing, ``np.sort`` ...) copies the array to the host once and keeps it
   there -- from then on it is an ndarray in all but name (views alias it,

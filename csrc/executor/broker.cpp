@@ -76,6 +76,13 @@ class HipDevice final : public broker::Device {
     int64_t (*compress_ws)();
     int (*compress_ws_init)(void*, hipStream_t);
     int (*compress)(int, const void*, const void*, int64_t, void*, int64_t, void*, hipStream_t);
+    // order statistics and histograms (csrc/kernels/stats.hip)
+    int64_t (*select_ws)();
+    int (*select_ws_init)(void*, hipStream_t);
+    int (*select)(int, const void*, int64_t, const int64_t*, int, void*, void*, hipStream_t);
+    int64_t (*hist_ws)();
+    int (*hist_ws_init)(void*, hipStream_t);
+    int (*histogram)(int, const void*, int64_t, const void*, int, void*, void*, hipStream_t);
   } bk{};
 
   // Per-session GPU resources, pooled across sessions: a stream, the
@@ -92,6 +99,11 @@ class HipDevice final : public broker::Device {
     double* slot = nullptr;
     void* axis_ws = nullptr;  // axis-reduction partials, allocated on first use
     void* compress_ws = nullptr;  // compaction counts and offsets, allocated on first use
+    // bk_select / bk_histogram: workspaces, and the scratch their results, edges
+    // and counts pass through (kStats*), allocated on first use
+    void* select_ws = nullptr;
+    void* hist_ws = nullptr;
+    char* stats = nullptr;
     // frees waiting for the stream work recorded before them (event, buffer)
     std::vector<std::pair<hipEvent_t, void*>> pending;
     std::vector<hipEvent_t> spare_events;
@@ -316,6 +328,12 @@ class HipDevice final : public broker::Device {
     if (!sym(lib_, "bk_compress_workspace_bytes", &bk.compress_ws) ||
         !sym(lib_, "bk_compress_workspace_init", &bk.compress_ws_init) || !sym(lib_, "bk_compress", &bk.compress))
       bk.compress = nullptr;
+    if (!sym(lib_, "bk_select_workspace_bytes", &bk.select_ws) ||
+        !sym(lib_, "bk_select_workspace_init", &bk.select_ws_init) || !sym(lib_, "bk_select", &bk.select))
+      bk.select = nullptr;
+    if (!sym(lib_, "bk_histogram_workspace_bytes", &bk.hist_ws) ||
+        !sym(lib_, "bk_histogram_workspace_init", &bk.hist_ws_init) || !sym(lib_, "bk_histogram", &bk.histogram))
+      bk.histogram = nullptr;
     return true;
   }
 
@@ -601,6 +619,55 @@ class HipDevice final : public broker::Device {
     const int64_t es = dt == broker::kDtBool ? 1 : elem_bytes(dt);
     return timed(s, pick(s, short_bytes(n, 2 * es + 2)),
                  [&](hipStream_t q) { return bk.compress((int)dt, x, m, n, y, cap, c->compress_ws, q); });
+  }
+  // order statistics and histograms: results, edges and counts pass through
+  // the session's device scratch (select results at 0, edges, then counts)
+  static constexpr int64_t kStatsEdgesAt = 512;
+  static constexpr int64_t kStatsCountsAt = kStatsEdgesAt + ((int64_t)broker::kMaxBins + 1) * 8;
+  static constexpr int64_t kStatsBytes = kStatsCountsAt + (int64_t)broker::kMaxBins * 8;
+  bool stats_scratch(Ctx* c) { return c->stats || bk.malloc_((void**)&c->stats, kStatsBytes) == 0; }
+  int select(uint32_t dt, const void* x, int64_t n, const int64_t* ranks, uint32_t nranks, double* out,
+             void* s) override {
+    Ctx* c = (Ctx*)s;
+    if (!bk.select) return broker::kBadArgument;
+    if (!stats_scratch(c)) return broker::kOutOfMemory;
+    if (!c->select_ws) {
+      if (bk.malloc_(&c->select_ws, bk.select_ws()) != 0) return broker::kOutOfMemory;
+      bk.select_ws_init(c->select_ws, c->s);
+    }
+    // one read of x per byte of the dtype
+    const int rc = timed(s, pick(s, short_bytes(n, elem_bytes(dt), (int)elem_bytes(dt))), [&](hipStream_t q) {
+      return bk.select((int)dt, x, n, ranks, (int)nranks, c->stats, c->select_ws, q);
+    });
+    if (rc != 0) return rc;
+    if (hipMemcpyAsync(out, c->stats, ((size_t)nranks + 1) * 8, hipMemcpyDeviceToHost, c->s) != hipSuccess || !wait(c))
+      return broker::kLaunchFailed;
+    return 0;
+  }
+  int histogram(uint32_t dt, const void* x, int64_t n, const double* edges, uint32_t bins, uint64_t* counts,
+                void* s) override {
+    Ctx* c = (Ctx*)s;
+    if (!bk.histogram) return broker::kBadArgument;
+    if (!stats_scratch(c)) return broker::kOutOfMemory;
+    if (!c->hist_ws) {
+      if (bk.malloc_(&c->hist_ws, bk.hist_ws()) != 0) return broker::kOutOfMemory;
+      bk.hist_ws_init(c->hist_ws, c->s);
+    }
+    hipStream_t q0 = pick(s, short_bytes(n, elem_bytes(dt)));
+    // (the caller's edges stay put until the wait below, or the one on the failure path)
+    if (hipMemcpyAsync(c->stats + kStatsEdgesAt, edges, ((size_t)bins + 1) * 8, hipMemcpyHostToDevice, q0) != hipSuccess)
+      return broker::kLaunchFailed;
+    const int rc = timed(s, q0, [&](hipStream_t q) {
+      return bk.histogram((int)dt, x, n, c->stats + kStatsEdgesAt, (int)bins, c->stats + kStatsCountsAt, c->hist_ws, q);
+    });
+    if (rc != 0) {
+      hipStreamSynchronize(q0);
+      return rc;
+    }
+    if (hipMemcpyAsync(counts, c->stats + kStatsCountsAt, (size_t)bins * 8, hipMemcpyDeviceToHost, c->s) != hipSuccess ||
+        !wait(c))
+      return broker::kLaunchFailed;
+    return 0;
   }
   const char* last_error() override { return bk.last_error ? bk.last_error() : ""; }
   void info(int64_t v[5]) override {

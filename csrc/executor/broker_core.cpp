@@ -16,7 +16,7 @@ const char* op_name(uint32_t op) {
                                       "bk.fill",     "bk.reduce", "bk.gemm",  "bk.transpose", "bk.sync",
                                       "bk.memstats", "bk.info",  "bk.copy",   "bk.rand_reduce", "bk.alloc_at",
                                       "bk.reduce_axis", "bk.gemm_fp", "bk.compare", "bk.compare_count",
-                                      "bk.mask_logical", "bk.where", "bk.compress"};
+                                      "bk.mask_logical", "bk.where", "bk.compress", "bk.select", "bk.histogram"};
   return op < sizeof(names) / sizeof(names[0]) ? names[op] : names[0];
 }
 
@@ -487,6 +487,53 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
       // the output is written up to the mask's count only: scrubbed first, like a read
       if (!will_read(bx) || !will_read(bm) || !will_read(by)) return kLaunchFailed;
       return dev_.compress(dt, bx->ptr, bm->ptr, n, by->ptr, cap, stream_);
+    }
+    case kSelect: {
+      const uint32_t dt = r.get<uint32_t>(), nranks = r.get<uint32_t>();
+      const uint64_t x = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      uint64_t need;
+      Buf* bx = lookup(x);
+      if (n <= 0 || dt > 2 || nranks < 1 || nranks > kMaxRanks || !mul_ok((uint64_t)n, dtype_size(dt), &need) || !bx ||
+          need > bx->size)
+        return kBadHandle;
+      if (r.n != (uint64_t)nranks * 8) return kProtocol;
+      int64_t ranks[kMaxRanks];
+      for (uint32_t i = 0; i < nranks; ++i) {
+        ranks[i] = r.get<int64_t>();
+        if (ranks[i] < 0 || ranks[i] >= n) return kBadHandle;
+      }
+      if (!will_read(bx)) return kLaunchFailed;
+      double v[kMaxRanks + 1] = {};
+      const int rc = dev_.select(dt, bx->ptr, n, ranks, nranks, v, stream_);
+      for (uint32_t i = 0; i <= nranks; ++i) put(out, v[i]);
+      return rc;
+    }
+    case kHistogram: {
+      const uint32_t dt = r.get<uint32_t>(), bins = r.get<uint32_t>();
+      const uint64_t x = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      uint64_t need;
+      Buf* bx = lookup(x);
+      if (n < 0 || dt > 2 || bins < 1 || bins > kMaxBins || !mul_ok((uint64_t)n, dtype_size(dt), &need) || !bx ||
+          need > bx->size)
+        return kBadHandle;
+      if (r.n != ((uint64_t)bins + 1) * 8) return kProtocol;
+      std::vector<double> edges(bins + 1);
+      for (uint32_t i = 0; i <= bins; ++i) {
+        edges[i] = r.get<double>();
+        // finite and non-decreasing (a NaN fails both comparisons' negations)
+        if (!(edges[i] >= -1.7976931348623157e308 && edges[i] <= 1.7976931348623157e308) ||
+            (i > 0 && !(edges[i] >= edges[i - 1])))
+          return kBadHandle;
+      }
+      if (!will_read(bx)) return kLaunchFailed;
+      std::vector<uint64_t> counts(bins, 0);
+      const int rc = dev_.histogram(dt, bx->ptr, n, edges.data(), bins, counts.data(), stream_);
+      for (uint32_t i = 0; i < bins; ++i) put(out, counts[i]);
+      return rc;
     }
     case kCopy: {
       const uint64_t d = r.get<uint64_t>(), doff = r.get<uint64_t>(), s = r.get<uint64_t>(), soff = r.get<uint64_t>(),

@@ -40,8 +40,19 @@ enum Op : uint32_t {
   //                 dt 0 / 1 / 2 or 6 (bool); out holds cap elements and is another buffer than x and mask
   // kReduce also takes dt 6 (a mask of n bytes) with op 0 (count), 3 (any), 4 (all).
   kCompare, kCompareCount, kMaskLogical, kWhere, kCompress,
+  // order statistics and histograms (csrc/kernels/stats.hip); x holds n elements of dt 0 / 1 / 2.
+  // Both reply, like kReduce, and the payload is exactly as long as nranks / bins announce.
+  //   kSelect       u32 dt | u32 nranks | u64 x | i64 n | nranks x i64 rank
+  //                 1 <= nranks <= kMaxRanks, n >= 1, every rank in [0, n); replies nranks + 1 f64:
+  //                 np.sort(x)[rank] widened to f64 for each rank, then the number of NaNs in x
+  //   kHistogram    u32 dt | u32 bins | u64 x | i64 n | (bins + 1) x f64 edge
+  //                 1 <= bins <= kMaxBins, n >= 0, edges finite and non-decreasing; replies bins u64:
+  //                 the elements v with edges[i] <= v < edges[i + 1] (the last bin closed on the right)
+  kSelect, kHistogram,
   kOpCount
 };
+constexpr uint32_t kMaxRanks = 32;   // = kMaxRanks, kMaxBins of csrc/kernels/stats.hip
+constexpr uint32_t kMaxBins = 4096;
 constexpr uint32_t kDtBool = 6;  // not a dtype_size() code: the mask ops size masks as n bytes themselves
 enum Status : int32_t {
   kOk = 0, kBadArgument = 1, kLaunchFailed = 2, kOutOfMemory = 3, kQuotaExceeded = 4, kNotInitialized = 5,
@@ -144,6 +155,14 @@ class Device {
   }
   // out[0 : min(count, cap)] = x[mask]; nothing at or past index cap is written
   virtual int compress(uint32_t, const void*, const void*, int64_t, void*, int64_t, void*) { return kBadArgument; }
+  // order statistics and histograms (bk_select, bk_histogram), synchronous
+  // like reduce.  select: ranks is nranks host i64, out nranks + 1 host f64
+  // (the values, then the NaN count); histogram: edges is bins + 1 host f64,
+  // counts bins host u64.  The session has validated every argument.
+  virtual int select(uint32_t, const void*, int64_t, const int64_t*, uint32_t, double*, void*) { return kBadArgument; }
+  virtual int histogram(uint32_t, const void*, int64_t, const double*, uint32_t, uint64_t*, void*) {
+    return kBadArgument;
+  }
   virtual int transpose(int sdt, int ddt, const void* in, void* out, int rows, int cols, int ldi, int ldo, void* s) = 0;
   // per-column (axis 0) / per-row (axis 1) sum or mean into y (f64 for f64 x, else f32)
   virtual int reduce_axis(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,

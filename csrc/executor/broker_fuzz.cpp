@@ -16,6 +16,7 @@
 #include <sys/un.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -143,6 +144,58 @@ class HostDevice final : public Device {
     if (!es || cap < 0) return kBadArgument;
     const double v = sum(x, (uint64_t)n * es) + sum(m, (uint64_t)n);
     touch_w(y, (uint64_t)cap * es, v > 0 ? 1 : 0);  // (the most the kernel may write: a mask of at least cap trues)
+    return 0;
+  }
+  // bk_select / bk_histogram: real answers from all n elements (widened to
+  // f64), so the replies can be checked against numpy
+  static bool widen_all(uint32_t dt, const void* x, int64_t n, std::vector<double>* v) {
+    if (dt > 2 || n < 0) return false;
+    v->resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      if (dt == 1) {
+        memcpy(&(*v)[i], (const char*)x + i * 8, 8);
+      } else {
+        uint32_t u = 0;
+        if (dt == 0) {
+          memcpy(&u, (const char*)x + i * 4, 4);
+        } else {
+          uint16_t h;
+          memcpy(&h, (const char*)x + i * 2, 2);
+          u = (uint32_t)h << 16;
+        }
+        float f;
+        memcpy(&f, &u, 4);
+        (*v)[i] = (double)f;
+      }
+    }
+    return true;
+  }
+  int select(uint32_t dt, const void* x, int64_t n, const int64_t* ranks, uint32_t nranks, double* out,
+             void*) override {
+    std::vector<double> v;
+    if (!widen_all(dt, x, n, &v) || n < 1 || nranks < 1 || nranks > kMaxRanks) return kBadArgument;
+    // numpy's sort order: NaNs last
+    std::sort(v.begin(), v.end(), [](double a, double b) { return a == a && (b != b || a < b); });
+    int64_t nans = 0;
+    for (double d : v) nans += d != d ? 1 : 0;
+    for (uint32_t i = 0; i < nranks; ++i) {
+      if (ranks[i] < 0 || ranks[i] >= n) return kBadArgument;
+      out[i] = v[(size_t)ranks[i]];
+    }
+    out[nranks] = (double)nans;
+    return 0;
+  }
+  int histogram(uint32_t dt, const void* x, int64_t n, const double* edges, uint32_t bins, uint64_t* counts,
+                void*) override {
+    std::vector<double> v;
+    if (!widen_all(dt, x, n, &v) || bins < 1 || bins > kMaxBins) return kBadArgument;
+    for (uint32_t i = 0; i < bins; ++i) counts[i] = 0;
+    for (double d : v) {
+      if (!(d >= edges[0] && d <= edges[bins])) continue;
+      // the last edge <= d; the last bin is closed on the right
+      size_t b = (size_t)(std::upper_bound(edges, edges + bins + 1, d) - edges) - 1;
+      counts[b < bins ? b : bins - 1] += 1;
+    }
     return 0;
   }
   int rand_reduce(uint32_t op, uint32_t dt, int64_t n, uint64_t, uint64_t, double, double, double* out, void*) override {

@@ -120,6 +120,68 @@ def mask_rows():
     row("torch tx[tm] f64, 50%", lambda: tx[tm], "torch", n * 10 + count * 8)
 
 
+def stats_rows():
+    """The radix select and the histogram (csrc/kernels/stats.hip), n = 1e8 f64
+    and f32, uniform / normal / all-equal data, each beside bk.sum of the same
+    array (how many array reads it costs) and its torch counterpart on the same
+    buffer: `python tools/bench_kernels.py stats` (profiles/stats_kernels.jsonl).
+    A select reads the array once per byte of the dtype."""
+    from bee_code_interpreter_fs_amd.ops.array import driver
+
+    bk.init()
+    emit(kernel="device", **bk.device_info())
+    drv = driver()
+    n = 10**8
+    for dtype, esize in (("float64", 8), ("float32", 4)):
+        for data in ("uniform", "normal", "equal"):
+            if data == "uniform":
+                x = bk.random.uniform(0.0, 1.0, n, dtype=dtype)._materialize()
+            elif data == "normal":
+                x = bk.random.normal(0.0, 1.0, n, dtype=dtype)._materialize()
+            else:
+                x = bk.full(n, 0.3, dtype)
+            tx = bk.to_torch(x)
+            tag = f"{dtype} {data}"
+
+            def row(kernel, fn, timer, reads=1, reps=10, **kw):
+                ms, mn, mx = spread(fn, timer, reps=reps, warmup=2)
+                emit(kernel=f"{kernel} [{tag}]", n=n, ms=ms, min_ms=mn, max_ms=mx, GBps=reads * n * esize / ms / 1e6, **kw)
+                return ms, mn, mx
+
+            s_ms, s_mn, s_mx = row("sum (driver call, incl. 8B readback)", lambda: drv.reduce(0, x.code, x.ptr, 0, n), "bk")
+            pair = [(n - 1) // 2, n // 2]
+            ten = [int(q * (n - 1)) for q in (0.001, 0.01, 0.05, 0.25, 0.4, 0.5, 0.75, 0.95, 0.99, 0.999)]
+            for name, ranks in (("select median pair", pair), ("select 10 ranks", ten)):
+                ms, _, _ = row(f"{name} ({esize} passes, incl. readback)", lambda: drv.select(x.code, x.ptr, n, ranks),
+                               "bk", reads=esize)
+                emit(kernel=f"{name} vs passes x sum [{tag}]", sums=ms / s_ms, passes=esize,
+                     within_passes_plus_spread=bool(ms <= esize * s_ms + (s_mx - s_mn)))
+            ms, _, _ = row("np.percentile(x, [1, 5, 50, 95, 99]) end to end", lambda: np.percentile(x, [1, 5, 50, 95, 99]),
+                           "bk", reads=esize)
+            emit(kernel=f"percentile vs sum [{tag}]", sums=ms / s_ms)
+            med_ms, _, _ = row("np.median(x) end to end", lambda: np.median(x), "bk", reads=esize)
+            t_ms, _, _ = row("torch.median", lambda: torch.median(tx).item(), "torch", reps=5)
+            emit(kernel=f"median vs torch.median [{tag}]", ratio=med_ms / t_ms)
+            row("torch.kthvalue(n // 2)", lambda: torch.kthvalue(tx, n // 2).values.item(), "torch", reps=5)
+            lo, hi = (0.0, 1.0) if data != "normal" else (-6.0, 6.0)
+            for bins in (50, 4096):
+                edges = np.linspace(lo, hi, bins + 1)
+                ms, _, _ = row(f"histogram {bins} bins (driver call, incl. edges up / counts back)",
+                               lambda: drv.histogram(x.code, x.ptr, n, edges), "bk")
+                emit(kernel=f"histogram {bins} vs sum [{tag}]", sums=ms / s_ms)
+                if dtype == "float32":
+                    t_ms, _, _ = row(f"torch.histc {bins} bins", lambda: torch.histc(tx, bins=bins, min=lo, max=hi)[0].item(),
+                                     "torch", reps=5)
+                    emit(kernel=f"histogram {bins} vs torch.histc [{tag}]", ratio=ms / t_ms)
+                try:
+                    t_ms, _, _ = row(f"torch.histogram {bins} bins",
+                                     lambda: torch.histogram(tx, bins=bins, range=(lo, hi))[0][0].item(), "torch", reps=5)
+                    emit(kernel=f"histogram {bins} vs torch.histogram [{tag}]", ratio=ms / t_ms)
+                except Exception as exc:  # (no device kernel in this torch build)
+                    emit(kernel=f"torch.histogram {bins} bins [{tag}]", error=type(exc).__name__)
+            del tx, x
+
+
 def emit(**kw):
     print(json.dumps(kw), flush=True)
 
@@ -205,4 +267,4 @@ def main():
 
 
 if __name__ == "__main__":
-    mask_rows() if sys.argv[1:] == ["masks"] else main()
+    mask_rows() if sys.argv[1:] == ["masks"] else stats_rows() if sys.argv[1:] == ["stats"] else main()
