@@ -4,7 +4,8 @@ Exposed to sandboxed code as the top-level module ``beekern`` (see
 ``runtime/sandbox_modules/beekern.py``).  Kernels: Philox RNG, elementwise
 (square & friends), deterministic reductions (sum, fused square-sum, dot,
 min/max), boolean masks (comparisons, fused counts, where, x[mask]), order statistics and
-histograms (median / percentile / quantile by radix select, np.histogram), bf16 MFMA GEMM and f64 / f32 MFMA GEMM at numpy's precision — source in ``csrc/kernels``.
+histograms (median / percentile / quantile by radix select, np.histogram), 2-D broadcasting and
+per-axis max / min / var / std, bf16 MFMA GEMM and f64 / f32 MFMA GEMM at numpy's precision — source in ``csrc/kernels``.
 """
 
 from ._native import BeekernError, QuotaExceeded, library_path  # noqa: F401
@@ -71,11 +72,13 @@ from .array import (  # noqa: F401
     sqrt,
     square,
     square_sum,
+    std,
     subtract,
     sum,
     synchronize,
     tanh,
     to_torch,
+    var,
     where,
     zeros,
 )

@@ -117,6 +117,10 @@ def _declare(lib: ctypes.CDLL) -> None:
         "bk_reduce_workspace_init": ([c_vp, c_vp], c_int),
         "bk_reduce_axis_workspace_init": ([c_vp, c_vp], c_int),
         "bk_reduce_axis": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp], c_int),
+        "bk_broadcast": ([c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp], c_int),
+        "bk_axis_stat_workspace_bytes": ([], c_i64),
+        "bk_axis_stat_workspace_init": ([c_vp, c_vp], c_int),
+        "bk_axis_stat": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_d, c_vp, c_vp, c_vp], c_int),
         "bk_gemm_bf16_fast_ok": ([c_int, c_int, c_int, c_int, c_int], c_int),
         "bk_gemm_bf16_tn": (
             [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_int, c_vp],

@@ -19,6 +19,12 @@ array without sorting or copying it (``csrc/kernels/stats.hip``: a radix
 select of a few ranks, a histogram counted in LDS); they read a ``.T`` view in
 place and return host scalars / ndarrays typed as numpy's.
 
+2-D arrays: the binary operations broadcast an ``(R, C)`` array against a
+``(C,)``, ``(1, C)`` or ``(R, 1)`` one of the same dtype in one pass, and
+``amax`` / ``amin`` / ``var`` / ``std`` (like ``sum`` / ``mean``) reduce along
+an axis, with ``keepdims`` (``csrc/kernels/axis.hip``; f32 / f64, ``.T`` views
+read in place).
+
 ``square`` (and ``x * x`` / ``x ** 2``) returns a *lazy* array: if the only
 consumer is a reduction the square is fused into it (no 800 MB temporary);
 any other use materialises it with the elementwise kernel.
@@ -321,17 +327,27 @@ class DeviceArray:
             driver().compress(self.code, self.ptr, key.ptr, self.size, out.ptr, count)
         return out
 
-    def sum(self, axis: Optional[int] = None):
-        return sum(self, axis)
+    def sum(self, axis: Optional[int] = None, keepdims: bool = False):
+        return sum(self, axis, keepdims)
 
-    def mean(self, axis: Optional[int] = None):
-        return mean(self, axis)
+    def mean(self, axis: Optional[int] = None, keepdims: bool = False):
+        return mean(self, axis, keepdims)
 
-    def max(self):
-        return _reduce("max", self)
+    def max(self, axis: Optional[int] = None, keepdims: bool = False):
+        if axis is None and not keepdims:
+            return _reduce("max", self)
+        return amax(self, axis, keepdims)
 
-    def min(self):
-        return _reduce("min", self)
+    def min(self, axis: Optional[int] = None, keepdims: bool = False):
+        if axis is None and not keepdims:
+            return _reduce("min", self)
+        return amin(self, axis, keepdims)
+
+    def var(self, axis: Optional[int] = None, ddof=0, keepdims: bool = False):
+        return var(self, axis, ddof, keepdims)
+
+    def std(self, axis: Optional[int] = None, ddof=0, keepdims: bool = False):
+        return std(self, axis, ddof, keepdims)
 
     def __add__(self, o): return _binary("add", self, o)
     def __radd__(self, o): return _binary("add", self, o)
@@ -532,21 +548,95 @@ def square(x) -> DeviceArray:
     return DeviceArray(x.shape, x.dtype, lazy=("square", x))
 
 
+def _vector_kind(matrix: DeviceArray, v: DeviceArray) -> Optional[int]:
+    """How ``v`` runs along the 2-D ``matrix`` under numpy's broadcasting:
+    0 for one element per column (shapes (C,) and (1, C)), 1 for one per row
+    ((R, 1)), None if it is no such vector."""
+    if matrix.ndim != 2:
+        return None
+    rows, cols = matrix.shape
+    if v.shape in ((cols,), (1, cols)):
+        return 0
+    if v.shape == (rows, 1):
+        return 1
+    return None
+
+
+def _broadcast_shape(s: Shape, t: Shape) -> Optional[Shape]:
+    """numpy's broadcast of two shapes, or None if they do not broadcast."""
+    n = max(len(s), len(t))
+    s, t = (1,) * (n - len(s)) + tuple(s), (1,) * (n - len(t)) + tuple(t)
+    out = []
+    for p, q in zip(s, t):
+        if p != q and 1 not in (p, q):
+            return None
+        out.append(q if p == 1 else p)
+    return tuple(out)
+
+
+def _broadcast(op: str, matrix: DeviceArray, v: DeviceArray, kind: int, swapped: bool) -> DeviceArray:
+    """``matrix op v`` (``v op matrix`` if swapped) with ``v`` along one axis
+    (bk_broadcast).  A ``.T`` view is read in place: its buffer takes the vector
+    along the other axis and the result is a ``.T`` view again."""
+    if matrix._lazy is not None:
+        matrix._materialize()
+    v._materialize()
+    rows, cols = matrix.shape
+    if matrix._transposed:  # the buffer is (cols, rows)
+        rows, cols, kind = cols, rows, 1 - kind
+    out = _Buffer(matrix.nbytes)
+    if matrix.size:
+        driver().broadcast(_BINARY[op], matrix.code, kind, swapped, matrix._buf.ptr, v.ptr, out.ptr,  # type: ignore[union-attr]
+                           rows, cols, cols, cols)
+    return DeviceArray(matrix.shape, matrix.dtype, buffer=out, strides_t=matrix._transposed)
+
+
+def _binary_unequal(op: str, a: DeviceArray, b: DeviceArray, reversed_: bool) -> Optional[DeviceArray]:
+    """``a op b`` (``b op a`` if reversed) for two arrays of one float dtype
+    whose shapes differ but broadcast to one of them; None if they do not."""
+    if a.ndim > 2 or b.ndim > 2:
+        return None
+    if a.size == b.size:  # e.g. (C,) with (1, C): the same elements in the same order
+        shape = _broadcast_shape(a.shape, b.shape)
+        if shape not in (a.shape, b.shape):
+            return None
+        a._materialize()
+        b._materialize()
+        if reversed_:
+            a, b = b, a
+        out = DeviceArray(shape, a.dtype)
+        driver().binary(_BINARY[op], a.code, 0, a.ptr, b.ptr, 0.0, out.ptr, a.size)
+        return out
+    if a.dtype not in ("float32", "float64"):
+        return None  # (bk_broadcast has no bf16 form)
+    kind = _vector_kind(a, b)
+    if kind is not None:
+        return _broadcast(op, a, b, kind, reversed_)
+    kind = _vector_kind(b, a)
+    if kind is not None:
+        return _broadcast(op, b, a, kind, not reversed_)
+    return None
+
+
 def _binary(op: str, a, b, reversed_: bool = False) -> DeviceArray:
     a = _as_operand(a)
     _no_masks(op, a)
-    a._materialize()
     if is_number(b):
+        a._materialize()
         out = DeviceArray(a.shape, a.dtype)
         driver().binary(_BINARY[op], a.code, 2 if reversed_ else 1, a.ptr, 0, float(b), out.ptr, a.size)
         return out
     b = _as_operand(b)
     _no_masks(op, b)
-    b._materialize()
     if b.shape != a.shape or b.dtype != a.dtype:
         if b.size == 1:
             return _binary(op, a, float(b.item()), reversed_)
-        raise ValueError(f"beekern {op}: shapes/dtypes must match ({a.shape} {a.dtype} vs {b.shape} {b.dtype})")
+        res = _binary_unequal(op, a, b, reversed_) if b.dtype == a.dtype else None
+        if res is None:
+            raise ValueError(f"beekern {op}: shapes/dtypes must match ({a.shape} {a.dtype} vs {b.shape} {b.dtype})")
+        return res
+    a._materialize()
+    b._materialize()
     if reversed_:
         a, b = b, a
     out = DeviceArray(a.shape, a.dtype)
@@ -593,8 +683,21 @@ def _reduce_axis(op: str, x: DeviceArray, axis: int):
     return out
 
 
-def sum(x, axis: Optional[int] = None):  # noqa: A001 - numpy-compatible name
+def _kept(res, x: DeviceArray, axis: Optional[int]):
+    """``res`` with the reduced axis kept as length one (numpy's
+    ``keepdims=True``): a reshape of an axis result, a one-element array of a
+    whole-array one."""
+    if isinstance(res, DeviceArray):
+        return res.reshape(1, res.size) if (axis + 2 if axis < 0 else axis) == 0 else res.reshape(res.size, 1)
+    return full((1,) * x.ndim, float(res), x.dtype)
+
+
+def sum(x, axis: Optional[int] = None, keepdims: bool = False):  # noqa: A001 - numpy-compatible name
     x = _as_operand(x)
+    if keepdims:
+        if x.dtype == "bool":
+            raise TypeError("beekern sum: keepdims of a bool array's count has no kernel")
+        return _kept(sum(x, axis), x, axis)
     if x.dtype == "bool":
         if axis is not None and not (x.ndim == 1 and axis in (0, -1)):
             raise TypeError("beekern sum: axis sums of a bool array have no kernel")
@@ -620,8 +723,12 @@ def square_sum(x) -> np.float64:
     return _reduce("square_sum", x._materialize())
 
 
-def mean(x, axis: Optional[int] = None):
+def mean(x, axis: Optional[int] = None, keepdims: bool = False):
     x = _as_operand(x)
+    if keepdims:
+        if x.dtype == "bool":
+            raise TypeError("beekern mean: keepdims of a bool array's mean has no kernel")
+        return _kept(mean(x, axis), x, axis)
     if x.dtype == "bool":
         if axis is not None and not (x.ndim == 1 and axis in (0, -1)):
             raise TypeError("beekern mean: axis means of a bool array have no kernel")
@@ -650,8 +757,104 @@ def max_abs_diff(a, b) -> np.float64:
     return _reduce("max_abs_diff", a, b)
 
 
-def amax(x): return _reduce("max", _as_operand(x)._materialize())
-def amin(x): return _reduce("min", _as_operand(x)._materialize())
+# ---- per-axis max / min / var / std (csrc/kernels/axis.hip) --------------------------
+
+_STAT = {"max": 0, "min": 1, "var": 2, "std": 3}
+MAX_AXIS0_COLUMNS = 1 << 18  # = kWsDoubles (axis.hip): the column form's workspace
+
+
+def _stat_axis(what: str, x: DeviceArray, axis) -> Optional[int]:
+    """The axis (0 or 1) of a 2-D array that ``what`` reduces along, or None
+    for the whole array (no axis, or the one axis of a 1-D array)."""
+    if axis is None:
+        return None
+    if not is_integer(axis):
+        raise TypeError(f"beekern {what}: axis is an int or None, got {type(axis).__name__}")
+    axis = int(axis)
+    if x.ndim == 1:
+        if axis not in (0, -1):
+            raise ValueError(f"axis {axis} is out of bounds for a 1-D array")
+        return None
+    if x.ndim != 2:
+        raise ValueError("axis reductions support 1-D and 2-D arrays")
+    if axis not in (0, 1, -1, -2):
+        raise ValueError(f"axis {axis} is out of bounds for a 2-D array")
+    return axis % 2
+
+
+def _axis_stat(what: str, x: DeviceArray, axis: int, ddof=0) -> DeviceArray:
+    """max / min / var / std of a 2-D f32 / f64 array along ``axis`` in the
+    array's dtype (bk_axis_stat: f64 arithmetic, the variance in two passes
+    about an f64 mean).  A ``.T`` view reduces along the other axis of its
+    buffer."""
+    if x.dtype not in ("float32", "float64"):
+        raise TypeError(f"beekern {what}: axis reductions take float32 / float64 arrays, got {x.dtype}")
+    if x._lazy is not None:
+        x._materialize()
+    rows, cols = x.shape
+    if x._transposed:  # the buffer is (cols, rows)
+        rows, cols, axis = cols, rows, 1 - axis
+    n = rows if axis == 0 else cols
+    if n == 0 or x.size == 0:
+        raise ValueError(f"beekern {what}: the reduced axis (or the array) is empty")
+    divisor = 1.0
+    if what in ("var", "std"):
+        divisor = float(n - ddof)
+        if not divisor > 0.0:
+            raise ValueError(f"beekern {what}: ddof {ddof} leaves no degrees of freedom along an axis of {n}")
+    if axis == 0 and cols > MAX_AXIS0_COLUMNS:
+        raise ValueError(f"beekern {what}: at most {MAX_AXIS0_COLUMNS} columns along axis 0 of the buffer, got {cols}")
+    out = DeviceArray((cols if axis == 0 else rows,), x.dtype)
+    driver().axis_stat(_STAT[what], x.code, x._buf.ptr, out.ptr, rows, cols, cols, axis, divisor)  # type: ignore[union-attr]
+    return out
+
+
+def _extremum(what: str, x, axis, keepdims: bool):
+    x = _as_operand(x)
+    ax = _stat_axis(what, x, axis)
+    if ax is None:
+        res = _reduce(what, x._materialize())
+    else:
+        res = _axis_stat(what, x, ax)
+    return _kept(res, x, ax) if keepdims else res
+
+
+def amax(x, axis: Optional[int] = None, keepdims: bool = False):
+    return _extremum("max", x, axis, keepdims)
+
+
+def amin(x, axis: Optional[int] = None, keepdims: bool = False):
+    return _extremum("min", x, axis, keepdims)
+
+
+def _spread(what: str, x, axis, ddof, keepdims: bool):
+    x = _as_operand(x)
+    if x.dtype not in ("float32", "float64"):
+        raise TypeError(f"beekern {what}: float32 / float64 arrays only, got {x.dtype}")
+    if isinstance(ddof, bool) or not isinstance(ddof, (int, float)):
+        raise TypeError(f"beekern {what}: ddof is a number, got {type(ddof).__name__}")
+    ax = _stat_axis(what, x, axis)
+    if ax is None:
+        n = x.size
+        if not n - ddof > 0:
+            raise ValueError(f"beekern {what}: ddof {ddof} leaves no degrees of freedom for {n} elements")
+        m = float(mean(x))
+        v = float(square_sum(_binary("subtract", x, m))) / (n - ddof)  # two passes, as numpy
+        res = _result_type(x.dtype)(math.sqrt(v) if what == "std" else v)
+    else:
+        res = _axis_stat(what, x, ax, ddof)
+    return _kept(res, x, ax) if keepdims else res
+
+
+def var(x, axis: Optional[int] = None, ddof=0, keepdims: bool = False):
+    """np.var: the whole array (a scalar of the array's dtype) or one axis of
+    a 2-D array; two passes in f64, as numpy's."""
+    return _spread("var", x, axis, ddof, keepdims)
+
+
+def std(x, axis: Optional[int] = None, ddof=0, keepdims: bool = False):
+    """np.std; see :func:`var`."""
+    return _spread("std", x, axis, ddof, keepdims)
 
 
 def _make_unary(name):

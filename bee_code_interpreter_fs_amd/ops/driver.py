@@ -50,6 +50,7 @@ class NativeDriver:
         self.ws = 0
         self.scalar = 0
         self.axis_ws = 0
+        self.axis_stat_ws = 0
         self.compress_ws = 0
         self.select_ws = 0
         self.hist_ws = 0
@@ -138,6 +139,25 @@ class NativeDriver:
             check(self.lib.bk_reduce_axis_workspace_init(_vp(self.axis_ws), self.stream), "bk_reduce_axis_workspace_init")
         check(self.lib.bk_reduce_axis(op, dt, _vp(x), rows, cols, ld, axis, _vp(y), _vp(self.axis_ws), self.stream),
               "bk_reduce_axis")
+
+    # ---- a matrix against a vector, per-axis statistics (csrc/kernels/axis.hip) -------
+    def broadcast(self, op: int, dt: int, kind: int, swapped: bool, a: int, v: int, y: int, rows: int, cols: int,
+                  lda: int, ldy: int) -> None:
+        """y[r, c] = a[r, c] OP v[c] (kind 0) or a[r, c] OP v[r] (kind 1); swapped: v OP a.
+        op: the codes of ``binary``; f32 / f64; y may be a itself."""
+        check(self.lib.bk_broadcast(op, dt, kind, int(bool(swapped)), _vp(a), rows, cols, lda, _vp(v), _vp(y), ldy,
+                                    self.stream), "bk_broadcast")
+
+    def axis_stat(self, op: int, dt: int, x: int, y: int, rows: int, cols: int, ld: int, axis: int,
+                  divisor: float) -> None:
+        """y = max (op 0) / min (1) / var (2) / std (3) of x[rows, cols] along ``axis``, in x's
+        dtype (f32 / f64); divisor: the variance's n - ddof."""
+        if not self.axis_stat_ws:
+            self.axis_stat_ws = self.malloc(self.lib.bk_axis_stat_workspace_bytes())
+            check(self.lib.bk_axis_stat_workspace_init(_vp(self.axis_stat_ws), self.stream),
+                  "bk_axis_stat_workspace_init")
+        check(self.lib.bk_axis_stat(op, dt, _vp(x), rows, cols, ld, axis, float(divisor), _vp(y),
+                                    _vp(self.axis_stat_ws), self.stream), "bk_axis_stat")
 
     # ---- boolean masks (csrc/kernels/mask.hip): one byte per element ----------------
     def compare(self, op: int, dt: int, mode: int, a: int, b: int, sc: float, y: int, n: int) -> None:
@@ -270,7 +290,7 @@ def _info_dict(v, arch: str) -> dict:
 
 (HELLO, ALLOC, FREE, WRITE, READ, RAND, UNARY, BINARY, CAST, FILL, REDUCE, GEMM, TRANSPOSE, SYNC, MEMSTATS, INFO,
  COPY, RAND_REDUCE, ALLOC_AT, REDUCE_AXIS, GEMM_FP, COMPARE, COMPARE_COUNT, MASK_LOGICAL, WHERE,
- COMPRESS, SELECT, HISTOGRAM) = range(1, 29)
+ COMPRESS, SELECT, HISTOGRAM, BROADCAST, AXIS_STAT) = range(1, 31)
 _HDR = struct.Struct("<IIQ")
 _NO_REPLY = 1  # request flag: no response unless a later request collects an error
 _RHDR = struct.Struct("<iIQ")
@@ -510,6 +530,14 @@ class BrokerDriver:
 
     def reduce_axis(self, op, dt, x, y, rows, cols, ld, axis) -> None:
         self._post(REDUCE_AXIS, struct.pack("<IIQQqqqII", op, dt, x, y, rows, cols, ld, axis, 0))
+
+    # a matrix against a vector, per-axis statistics: payload layouts in broker_core.hpp
+    def broadcast(self, op, dt, kind, swapped, a, v, y, rows, cols, lda, ldy) -> None:
+        self._post(BROADCAST, struct.pack("<IIIIQQQqqqq", op, dt, kind, 1 if swapped else 0, a, v, y, rows, cols, lda,
+                                          ldy))
+
+    def axis_stat(self, op, dt, x, y, rows, cols, ld, axis, divisor) -> None:
+        self._post(AXIS_STAT, struct.pack("<IIQQqqqIId", op, dt, x, y, rows, cols, ld, axis, 0, float(divisor)))
 
     # boolean masks: payload layouts beside the op enum in csrc/executor/broker_core.hpp
     def compare(self, op, dt, mode, a, b, sc, y, n) -> None:

@@ -7,7 +7,10 @@ what numpy would (same dtype rules, same shape):
 * ufuncs: square, negative, absolute, sqrt, exp, log, sin, cos, tanh, add,
   subtract, multiply, divide, maximum, minimum, power -- elementwise kernels
   (``ops/array.py`` ``_unary`` / ``_binary``); ``np.square`` stays lazy, so
-  ``np.sum(np.square(x))`` is the fused one-pass square-sum;
+  ``np.sum(np.square(x))`` is the fused one-pass square-sum; the binary ones
+  also broadcast a 2-D ``(R, C)`` operand against a ``(C,)``, ``(1, C)`` or
+  ``(R, 1)`` one of the same dtype, on either side (``X - X.mean(axis=0)``:
+  one pass of ``csrc/kernels/axis.hip``, ``.T`` views read in place);
 * comparisons ``less`` / ``less_equal`` / ``greater`` / ``greater_equal`` /
   ``equal`` / ``not_equal`` of two device arrays or an array and a scalar
   (either side): a device ``bool`` mask, lazy until something other than a
@@ -19,12 +22,18 @@ what numpy would (same dtype rules, same shape):
   ``logical_not`` and ``bitwise_and`` / ``bitwise_or`` / ``bitwise_xor`` /
   ``invert`` (``&``, ``|``, ``^``, ``~``);
 * ufunc reductions ``np.add.reduce`` / ``np.maximum.reduce`` /
-  ``np.minimum.reduce``;
-* functions: ``sum`` / ``mean`` (whole array or one axis of a 2-D array),
-  ``max`` / ``min`` / ``amax`` / ``amin``, ``dot`` of 1-D vectors, ``var`` /
-  ``std`` (two passes, as numpy), ``linalg.norm`` (fused square-sum),
-  ``copy`` / ``reshape`` / ``ravel``, and the metadata functions
-  ``shape`` / ``ndim`` / ``size``;
+  ``np.minimum.reduce`` (whole array, or ``axis=0|1`` of a 2-D array);
+* functions: ``sum`` / ``mean``, ``max`` / ``min`` / ``amax`` / ``amin``,
+  ``var`` / ``std`` (``ddof`` too; two passes in f64, as numpy) of the whole
+  array or along one axis (``0``, ``1``, ``-1``, ``-2``) of a 2-D array, with
+  ``keepdims`` -- the axis forms of max / min / var / std take f32 / f64 and
+  run on ``csrc/kernels/axis.hip``; results are typed as numpy types them (an
+  array in the input dtype, a numpy scalar for a whole or 1-D array);
+  ``out=``, ``dtype=``, ``where=``, ``initial=``, tuple axes, ``mean=`` /
+  ``correction=`` and arrays of more than two dimensions go to the host;
+* ``dot`` of 1-D vectors, ``linalg.norm`` (fused square-sum), ``copy`` /
+  ``reshape`` / ``ravel``, and the metadata functions ``shape`` / ``ndim`` /
+  ``size``;
 * masks: ``sum`` (``np.int64``) / ``mean`` / ``count_nonzero`` (also of a
   float array: the fused ``!= 0`` count) / ``any`` / ``all`` of a whole
   array, and the three-argument ``where(mask, x, y)``;
@@ -255,7 +264,8 @@ def _try_ufunc(b, A, ufunc, name, method, inputs, kwargs, extra) -> Optional[Any
             if len(out) != 1 or b.dev(out[0]) is None:
                 return None
             o = b.dev(out[0])
-            if o.dtype != dt or o.shape != arrays[0].shape or o._transposed:
+            shape = arrays[0].shape if len(arrays) == 1 else A._broadcast_shape(arrays[0].shape, arrays[1].shape)
+            if o.dtype != dt or o.shape != shape or o._transposed:
                 return None
             o._materialize()  # (a lazy draw gets its buffer: the result is written into it)
         if name in _UNARY and len(inputs) == 1:
@@ -265,7 +275,8 @@ def _try_ufunc(b, A, ufunc, name, method, inputs, kwargs, extra) -> Optional[Any
             x, y = devs
             if x is not None and y is not None:
                 if x.shape != y.shape:
-                    return None
+                    # a matrix against a vector along one axis, or two shapes of the same elements
+                    return None if 1 in (x.size, y.size) else A._binary_unequal(_BINARY[name], x, y, False)
                 if name == "multiply" and inputs[0] is inputs[1]:
                     return A.square(x)
                 return A._binary(_BINARY[name], x, y)
@@ -285,10 +296,26 @@ def _try_ufunc(b, A, ufunc, name, method, inputs, kwargs, extra) -> Optional[Any
         axis = kwargs.get("axis", 0)
         if axis is None or (x.ndim == 1 and axis in (0, -1)):
             return _full_reduce(A, _REDUCE[name], x)
-        if name == "add" and x.ndim == 2 and axis in (0, 1, -1, -2):
-            return A.sum(x, axis=axis)
+        if x.ndim == 2 and _is_axis(axis, (0, 1, -1, -2)):
+            if name == "add":
+                return A.sum(x, axis=axis)
+            if x.dtype in _FP:
+                return _axis_result(lambda: A.amax(x, axis) if name == "maximum" else A.amin(x, axis))
         return None
     return None
+
+
+def _is_axis(axis, allowed) -> bool:
+    return isinstance(axis, (int, np.integer)) and not isinstance(axis, (bool, np.bool_)) and axis in allowed
+
+
+def _axis_result(fn):
+    """An axis reduction's device result, or None where the ops layer refuses
+    it (an empty axis, too many columns, ddof >= n): numpy decides, on the host."""
+    try:
+        return fn()
+    except (ValueError, TypeError):
+        return None
 
 
 def _try_mask_ufunc(A, name, inputs, devs, dt) -> Optional[Any]:
@@ -336,6 +363,14 @@ def _given(v) -> bool:
 
 def _kw_only(kwargs, allowed) -> bool:
     return all(k in allowed or not _given(v) or (k == "keepdims" and v is False) for k, v in kwargs.items())
+
+
+def _keepdims(got) -> Optional[bool]:
+    """The call's ``keepdims`` (False when left out); None if it is no bool."""
+    k = got.get("keepdims", False)
+    if not _given(k):
+        return False
+    return bool(k) if isinstance(k, (bool, np.bool_)) else None
 
 
 def _bind(func_name: str, args, kwargs, params):
@@ -457,42 +492,66 @@ def _try_function(b, A, name, mod, args, kwargs):
         return {"shape": d.shape, "ndim": d.ndim, "size": d.size}[name]
     if name in ("sum", "mean"):
         got = _bind(name, args, kwargs, ("a", "axis", "dtype", "out", "keepdims"))
-        if got is None or not _kw_only(got, {"a", "axis"}):
+        if got is None or not _kw_only(got, {"a", "axis", "keepdims"}):
             return _NO
         x = b.dev(got["a"])
-        if x is None:
+        keep = _keepdims(got)
+        if x is None or keep is None:
             return _NO
+        fn = A.sum if name == "sum" else A.mean
         axis = got.get("axis")
-        if axis is None or (x.ndim == 1 and axis in (0, -1)):
-            v = A.sum(x) if name == "sum" else A.mean(x)
-            return _as_result_scalar(v, x.dtype)
+        if axis is None or (x.ndim == 1 and _is_axis(axis, (0, -1))):
+            if keep:  # a one-element array of the input's dimensions
+                return _NO if x.dtype == "bool" or x.ndim > 2 else b.box(fn(x, None, True))
+            return _as_result_scalar(fn(x), x.dtype)
         if x.dtype == "bool":
             return _NO
-        if x.ndim == 2 and isinstance(axis, int) and axis in (0, 1, -1, -2):
-            return b.box(A.sum(x, axis=axis) if name == "sum" else A.mean(x, axis=axis))
+        if x.ndim == 2 and _is_axis(axis, (0, 1, -1, -2)):
+            return b.box(fn(x, int(axis), keep))
         return _NO
     if name in ("max", "min", "amax", "amin"):
         got = _bind(name, args, kwargs, ("a", "axis", "out", "keepdims"))
-        if got is None or not _kw_only(got, {"a"}):
+        if got is None or not _kw_only(got, {"a", "axis", "keepdims"}):
             return _NO
         x = b.dev(got["a"])
-        if x is None:
+        keep = _keepdims(got)
+        if x is None or keep is None:
             return _NO
-        return _full_reduce(A, "amax" if name in ("max", "amax") else "amin", x)
+        what = "amax" if name in ("max", "amax") else "amin"
+        axis = got.get("axis")
+        if not _given(axis) or (x.ndim == 1 and _is_axis(axis, (0, -1))):
+            if not keep:
+                return _full_reduce(A, what, x)
+            axis = None
+        elif not (x.ndim == 2 and _is_axis(axis, (0, 1, -1, -2))):
+            return _NO
+        if x.dtype not in _FP or x.ndim > 2:
+            return _NO
+        res = _axis_result(lambda: getattr(A, what)(x, None if axis is None else int(axis), keep))
+        return _NO if res is None else b.box(res)
     if name in ("var", "std"):
         got = _bind(name, args, kwargs, ("a", "axis", "dtype", "out", "ddof", "keepdims"))
-        if got is None or not _kw_only(got, {"a", "ddof"}):
+        if got is None or not _kw_only(got, {"a", "axis", "ddof", "keepdims"}):
             return _NO
         x = b.dev(got["a"])
+        keep = _keepdims(got)
         ddof = got.get("ddof", 0) if _given(got.get("ddof")) else 0
-        if x is None or x.dtype in ("bfloat16", "bool") or not isinstance(ddof, (int, float)):
+        if x is None or keep is None or x.dtype in ("bfloat16", "bool") or isinstance(ddof, bool) or \
+                not isinstance(ddof, (int, float)):
             return _NO
+        axis = got.get("axis")
+        if _given(axis) and not (x.ndim == 1 and _is_axis(axis, (0, -1))):
+            if not (x.ndim == 2 and _is_axis(axis, (0, 1, -1, -2))):
+                return _NO
+            res = _axis_result(lambda: getattr(A, name)(x, int(axis), ddof, keep))
+            return _NO if res is None else b.box(res)
         n = x.size
-        if n - ddof <= 0:
+        if n - ddof <= 0 or (keep and x.ndim > 2):
             return _NO
         m = float(A.mean(x))
         v = float(A.square_sum(A._binary("subtract", x, m))) / (n - ddof)  # two passes, as numpy
-        return _as_result_scalar(math.sqrt(v) if name == "std" else v, x.dtype)
+        v = _as_result_scalar(math.sqrt(v) if name == "std" else v, x.dtype)
+        return b.box(A._kept(v, x, None)) if keep else v
     if name == "norm" and mod.endswith("linalg"):
         got = _bind(name, args, kwargs, ("x", "ord", "axis", "keepdims"))
         if got is None or not _kw_only(got, {"x"}):

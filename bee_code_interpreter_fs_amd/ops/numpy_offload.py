@@ -37,6 +37,10 @@ What the user sees:
   "linear") and ``np.histogram`` of a device-resident array run on the GPU (a
   radix select, a histogram in LDS) and return numpy's scalars / ndarrays;
   the array stays on the device (``examples/monte_carlo_var.py``);
+* tables: a 2-D draw broadcasts against a ``(C,)``, ``(1, C)`` or ``(R, 1)``
+  array in the arithmetic operators, and ``sum`` / ``mean`` / ``max`` /
+  ``min`` / ``var`` / ``std`` take ``axis`` and ``keepdims`` on the device
+  (``examples/standardize_softmax.py``);
 * semantics: the first operation without a GPU kernel (any other indexing, slicing,
   printing, ``np.sort`` ...) copies the array to the host once and keeps it
   there -- from then on it is an ndarray in all but name (views alias it,

@@ -83,6 +83,11 @@ class HipDevice final : public broker::Device {
     int64_t (*hist_ws)();
     int (*hist_ws_init)(void*, hipStream_t);
     int (*histogram)(int, const void*, int64_t, const void*, int, void*, void*, hipStream_t);
+    // a matrix against a vector, per-axis statistics (csrc/kernels/axis.hip)
+    int (*broadcast)(int, int, int, int, const void*, int64_t, int64_t, int64_t, const void*, void*, int64_t, hipStream_t);
+    int64_t (*axis_stat_ws)();
+    int (*axis_stat_ws_init)(void*, hipStream_t);
+    int (*axis_stat)(int, int, const void*, int64_t, int64_t, int64_t, int, double, void*, void*, hipStream_t);
   } bk{};
 
   // Per-session GPU resources, pooled across sessions: a stream, the
@@ -99,6 +104,7 @@ class HipDevice final : public broker::Device {
     double* slot = nullptr;
     void* axis_ws = nullptr;  // axis-reduction partials, allocated on first use
     void* compress_ws = nullptr;  // compaction counts and offsets, allocated on first use
+    void* axis_stat_ws = nullptr;  // bk_axis_stat's partials, column means and tickets, allocated on first use
     // bk_select / bk_histogram: workspaces, and the scratch their results, edges
     // and counts pass through (kStats*), allocated on first use
     void* select_ws = nullptr;
@@ -334,6 +340,10 @@ class HipDevice final : public broker::Device {
     if (!sym(lib_, "bk_histogram_workspace_bytes", &bk.hist_ws) ||
         !sym(lib_, "bk_histogram_workspace_init", &bk.hist_ws_init) || !sym(lib_, "bk_histogram", &bk.histogram))
       bk.histogram = nullptr;
+    sym(lib_, "bk_broadcast", &bk.broadcast);
+    if (!sym(lib_, "bk_axis_stat_workspace_bytes", &bk.axis_stat_ws) ||
+        !sym(lib_, "bk_axis_stat_workspace_init", &bk.axis_stat_ws_init) || !sym(lib_, "bk_axis_stat", &bk.axis_stat))
+      bk.axis_stat = nullptr;
     return true;
   }
 
@@ -581,6 +591,26 @@ class HipDevice final : public broker::Device {
     // ~10 us -- short next to the GEMM that produced it
     return timed(s, pick(s, short_bytes(rows * ld, elem_bytes(dt)) || rows * ld <= (16ll << 20)),
                  [&](hipStream_t q) { return bk.reduce_axis((int)op, (int)dt, x, rows, cols, ld, (int)axis, y, c->axis_ws, q); });
+  }
+  int broadcast(uint32_t op, uint32_t dt, uint32_t kind, bool swapped, const void* a, const void* v, void* y,
+                int64_t rows, int64_t cols, int64_t lda, int64_t ldy, void* s) override {
+    if (!bk.broadcast) return broker::kBadArgument;
+    return timed(s, pick(s, short_bytes(rows * cols, elem_bytes(dt), 2)), [&](hipStream_t q) {
+      return bk.broadcast((int)op, (int)dt, (int)kind, swapped ? 1 : 0, a, rows, cols, lda, v, y, ldy, q);
+    });
+  }
+  int axis_stat(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld, uint32_t axis,
+                double divisor, void* s) override {
+    Ctx* c = (Ctx*)s;
+    if (!bk.axis_stat) return broker::kBadArgument;
+    if (!c->axis_stat_ws) {
+      if (bk.malloc_(&c->axis_stat_ws, bk.axis_stat_ws()) != 0) return broker::kOutOfMemory;
+      bk.axis_stat_ws_init(c->axis_stat_ws, c->s);
+    }
+    // (the variance reads the matrix twice)
+    return timed(s, pick(s, short_bytes(rows * cols, elem_bytes(dt), op >= 2 ? 2 : 1)), [&](hipStream_t q) {
+      return bk.axis_stat((int)op, (int)dt, x, rows, cols, ld, (int)axis, divisor, y, c->axis_stat_ws, q);
+    });
   }
   // boolean masks: a mask is one byte per element
   int compare(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double sc, void* y, int64_t n,

@@ -16,7 +16,8 @@ const char* op_name(uint32_t op) {
                                       "bk.fill",     "bk.reduce", "bk.gemm",  "bk.transpose", "bk.sync",
                                       "bk.memstats", "bk.info",  "bk.copy",   "bk.rand_reduce", "bk.alloc_at",
                                       "bk.reduce_axis", "bk.gemm_fp", "bk.compare", "bk.compare_count",
-                                      "bk.mask_logical", "bk.where", "bk.compress", "bk.select", "bk.histogram"};
+                                      "bk.mask_logical", "bk.where", "bk.compress", "bk.select", "bk.histogram",
+                                      "bk.broadcast", "bk.axis_stat"};
   return op < sizeof(names) / sizeof(names[0]) ? names[op] : names[0];
 }
 
@@ -534,6 +535,41 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
       const int rc = dev_.histogram(dt, bx->ptr, n, edges.data(), bins, counts.data(), stream_);
       for (uint32_t i = 0; i < bins; ++i) put(out, counts[i]);
       return rc;
+    }
+    case kBroadcast: {
+      const uint32_t bop = r.get<uint32_t>(), dt = r.get<uint32_t>(), kind = r.get<uint32_t>(), swapped = r.get<uint32_t>();
+      const uint64_t a = r.get<uint64_t>(), v = r.get<uint64_t>(), y = r.get<uint64_t>();
+      const int64_t rows = r.get<int64_t>(), cols = r.get<int64_t>(), lda = r.get<int64_t>(), ldy = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      uint64_t na, ny, nv;
+      Buf *ba = lookup(a), *bv = lookup(v), *by = lookup(y);
+      if (bop > 6 || dt > 1 || kind > 1 || swapped > 1 || !matrix_bytes(rows, cols, lda, dtype_size(dt), &na) ||
+          !matrix_bytes(rows, cols, ldy, dtype_size(dt), &ny) ||
+          !mul_ok((uint64_t)(kind == 0 ? cols : rows), dtype_size(dt), &nv) || !ba || !bv || !by || na > ba->size ||
+          nv > bv->size || ny > by->size || by == bv || (by == ba && ldy != lda))
+        return kBadHandle;
+      // y's gaps (ldy > cols) are not written: they keep their scrub state
+      if (!will_read(ba) || !will_read(bv) || !(ldy == cols ? will_write(by, 0, ny) : will_read(by))) return kLaunchFailed;
+      return dev_.broadcast(bop, dt, kind, swapped != 0, ba->ptr, bv->ptr, by->ptr, rows, cols, lda, ldy, stream_);
+    }
+    case kAxisStat: {
+      const uint32_t sop = r.get<uint32_t>(), dt = r.get<uint32_t>();
+      const uint64_t x = r.get<uint64_t>(), y = r.get<uint64_t>();
+      const int64_t rows = r.get<int64_t>(), cols = r.get<int64_t>(), ld = r.get<int64_t>();
+      const uint32_t axis = r.get<uint32_t>();
+      r.get<uint32_t>();
+      const double divisor = r.get<double>();
+      if (!r.ok) return kProtocol;
+      uint64_t nx, ny;
+      Buf *bx = lookup(x), *by = lookup(y);
+      // (a NaN divisor fails both comparisons)
+      if (sop > 3 || dt > 1 || axis > 1 || !(divisor > 0.0 && divisor <= 1.7976931348623157e308) ||
+          !matrix_bytes(rows, cols, ld, dtype_size(dt), &nx) ||
+          !mul_ok((uint64_t)(axis == 0 ? cols : rows), dtype_size(dt), &ny) || !bx || !by || nx > bx->size ||
+          ny > by->size || by == bx)
+        return kBadHandle;
+      if (!will_read(bx) || !will_write(by, 0, ny)) return kLaunchFailed;
+      return dev_.axis_stat(sop, dt, bx->ptr, by->ptr, rows, cols, ld, axis, divisor, stream_);
     }
     case kCopy: {
       const uint64_t d = r.get<uint64_t>(), doff = r.get<uint64_t>(), s = r.get<uint64_t>(), soff = r.get<uint64_t>(),

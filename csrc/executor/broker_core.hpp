@@ -49,6 +49,17 @@ enum Op : uint32_t {
   //                 1 <= bins <= kMaxBins, n >= 0, edges finite and non-decreasing; replies bins u64:
   //                 the elements v with edges[i] <= v < edges[i + 1] (the last bin closed on the right)
   kSelect, kHistogram,
+  // 2-D arrays (csrc/kernels/axis.hip), dt 0 f32 / 1 f64 only; a matrix of rows x cols elements with
+  // row stride ld spans (rows - 1) * ld + cols of them.
+  //   kBroadcast    u32 op | u32 dt | u32 kind | u32 swapped | u64 a | u64 v | u64 y | i64 rows | i64 cols |
+  //                 i64 lda | i64 ldy
+  //                 y[r][c] = a[r][c] op v[c] (kind 0, v holds cols elements) or a[r][c] op v[r] (kind 1, rows
+  //                 elements); swapped 1: v op a; op: kBinary's codes 0..6; y may be a (then ldy == lda),
+  //                 never v
+  //   kAxisStat     u32 op | u32 dt | u64 x | u64 y | i64 rows | i64 cols | i64 ld | u32 axis | u32 0 | f64 divisor
+  //                 op 0 max, 1 min, 2 variance, 3 standard deviation along axis 0 (y: cols elements of dt)
+  //                 or 1 (rows elements); divisor: the variance's n - ddof, finite and > 0 for every op
+  kBroadcast, kAxisStat,
   kOpCount
 };
 constexpr uint32_t kMaxRanks = 32;   // = kMaxRanks, kMaxBins of csrc/kernels/stats.hip
@@ -161,6 +172,15 @@ class Device {
   // counts bins host u64.  The session has validated every argument.
   virtual int select(uint32_t, const void*, int64_t, const int64_t*, uint32_t, double*, void*) { return kBadArgument; }
   virtual int histogram(uint32_t, const void*, int64_t, const double*, uint32_t, uint64_t*, void*) {
+    return kBadArgument;
+  }
+  // a matrix against a vector along one axis, per-axis max / min / var / std
+  // (bk_broadcast, bk_axis_stat); kBadArgument where the device has no such kernel
+  virtual int broadcast(uint32_t, uint32_t, uint32_t, bool, const void*, const void*, void*, int64_t, int64_t, int64_t,
+                        int64_t, void*) {
+    return kBadArgument;
+  }
+  virtual int axis_stat(uint32_t, uint32_t, const void*, void*, int64_t, int64_t, int64_t, uint32_t, double, void*) {
     return kBadArgument;
   }
   virtual int transpose(int sdt, int ddt, const void* in, void* out, int rows, int cols, int ldi, int ldo, void* s) = 0;

@@ -17,6 +17,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -258,6 +259,77 @@ class HostDevice final : public Device {
     const uint64_t es = dtype_size(dt), os = dt == 1 ? 8 : 4;
     for (int64_t r = 0; r < rows; ++r) sum((const char*)x + (uint64_t)r * ld * es, (uint64_t)cols * es);
     touch_w(y, (uint64_t)(axis == 0 ? cols : rows) * os, 0);
+    return 0;
+  }
+  // bk_broadcast / bk_axis_stat: real answers (f32 / f64), every element of
+  // every row read and written where the kernels would
+  template <typename T>
+  static T bin(uint32_t op, T a, T b) {
+    switch (op) {
+      case 0: return a + b;
+      case 1: return a - b;
+      case 2: return a * b;
+      case 3: return a / b;
+      case 4: return (a > b || a != a) ? a : b;
+      case 5: return (a < b || a != a) ? a : b;
+    }
+    return (T)std::pow(a, b);
+  }
+  template <typename T>
+  static T at(const void* p, int64_t i) {
+    T v;
+    memcpy(&v, (const char*)p + (uint64_t)i * sizeof(T), sizeof(T));
+    return v;
+  }
+  template <typename T>
+  static void set(void* p, int64_t i, T v) {
+    memcpy((char*)p + (uint64_t)i * sizeof(T), &v, sizeof(T));
+  }
+  template <typename T>
+  static void broadcast_t(uint32_t op, uint32_t kind, bool swapped, const void* a, const void* v, void* y, int64_t rows,
+                          int64_t cols, int64_t lda, int64_t ldy) {
+    for (int64_t r = 0; r < rows; ++r)
+      for (int64_t c = 0; c < cols; ++c) {
+        const T x = at<T>(a, r * lda + c), w = at<T>(v, kind == 0 ? c : r);
+        set<T>(y, r * ldy + c, swapped ? bin<T>(op, w, x) : bin<T>(op, x, w));
+      }
+  }
+  int broadcast(uint32_t op, uint32_t dt, uint32_t kind, bool swapped, const void* a, const void* v, void* y,
+                int64_t rows, int64_t cols, int64_t lda, int64_t ldy, void*) override {
+    if (op > 6 || dt > 1 || kind > 1 || rows < 0 || cols < 0 || lda < cols || ldy < cols) return kBadArgument;
+    if (dt == 1) broadcast_t<double>(op, kind, swapped, a, v, y, rows, cols, lda, ldy);
+    else broadcast_t<float>(op, kind, swapped, a, v, y, rows, cols, lda, ldy);
+    return 0;
+  }
+  template <typename T>
+  static void axis_stat_t(uint32_t op, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld, uint32_t axis,
+                          double divisor) {
+    const int64_t lines = axis == 0 ? cols : rows, len = axis == 0 ? rows : cols;
+    for (int64_t i = 0; i < lines; ++i) {
+      auto elem = [&](int64_t k) { return (double)(axis == 0 ? at<T>(x, k * ld + i) : at<T>(x, i * ld + k)); };
+      double res;
+      if (op < 2) {
+        res = elem(0);
+        for (int64_t k = 1; k < len; ++k) {
+          const double e = elem(k);
+          res = op == 0 ? ((res > e || res != res) ? res : e) : ((res < e || res != res) ? res : e);
+        }
+      } else {
+        double sum = 0, ss = 0;
+        for (int64_t k = 0; k < len; ++k) sum += elem(k);
+        const double mean = sum / (double)len;
+        for (int64_t k = 0; k < len; ++k) ss += (elem(k) - mean) * (elem(k) - mean);
+        res = op == 3 ? std::sqrt(ss / divisor) : ss / divisor;
+      }
+      set<T>(y, i, (T)res);
+    }
+  }
+  int axis_stat(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld, uint32_t axis,
+                double divisor, void*) override {
+    if (op > 3 || dt > 1 || axis > 1 || rows <= 0 || cols <= 0 || ld < cols || !(divisor > 0)) return kBadArgument;
+    if (axis == 0 && cols > 262144) return kBadArgument;  // the device's column workspace (axis.hip)
+    if (dt == 1) axis_stat_t<double>(op, x, y, rows, cols, ld, axis, divisor);
+    else axis_stat_t<float>(op, x, y, rows, cols, ld, axis, divisor);
     return 0;
   }
   const char* last_error() override { return "host device"; }

@@ -5,6 +5,7 @@
 // (bk_common.hpp ld16/st16), grid-stride over <= 64 blocks per CU.  bf16 math runs in f32
 // and rounds once on store.  `numpy.square` of the benchmark payload
 // (`examples/benchmark-numpy.py:21`) is kUnarySquare on f64.
+#include "bk_binary_op.hpp"  // BinaryOp and binary<OP>, shared with axis.hip
 #include "bk_common.hpp"
 
 namespace bk {
@@ -13,7 +14,6 @@ enum UnaryOp : int {
   kUnarySquare = 0, kUnaryAbs, kUnaryNeg, kUnarySqrt, kUnaryExp, kUnaryLog, kUnaryRelu,
   kUnarySin, kUnaryCos, kUnaryTanh, kUnarySigmoid, kUnaryCopy, kUnaryCount
 };
-enum BinaryOp : int { kBinAdd = 0, kBinSub, kBinMul, kBinDiv, kBinMax, kBinMin, kBinPow, kBinCount };
 
 template <typename T> struct Elem;  // storage <-> compute type
 template <> struct Elem<float> {
@@ -46,18 +46,6 @@ __device__ __forceinline__ C unary(C x) {
   else if constexpr (OP == kUnaryTanh) return tanh(x);
   else if constexpr (OP == kUnarySigmoid) return C(1) / (C(1) + exp(-x));
   else return x;
-}
-
-template <int OP, typename C>
-__device__ __forceinline__ C binary(C a, C b) {
-  if constexpr (OP == kBinAdd) return a + b;
-  else if constexpr (OP == kBinSub) return a - b;
-  else if constexpr (OP == kBinMul) return a * b;
-  else if constexpr (OP == kBinDiv) return a / b;
-  // numpy.maximum / minimum: NaN in either operand gives NaN
-  else if constexpr (OP == kBinMax) return (a > b || a != a) ? a : b;
-  else if constexpr (OP == kBinMin) return (a < b || a != a) ? a : b;
-  else return pow(a, b);
 }
 
 template <typename T>

@@ -182,6 +182,56 @@ def stats_rows():
             del tx, x
 
 
+def axis_rows():
+    """The broadcast and the axis statistics (csrc/kernels/axis.hip) on
+    10000 x 10000 f64 and f32 and a tall 10^7 x 8 f64 table, uniform data:
+    `python tools/bench_kernels.py axis` (profiles/axis_kernels.jsonl).  Each
+    new operation beside a yardstick measured in the same run: X - v beside
+    bk.subtract of two equal-shape arrays (which moves half as much again),
+    max(axis) beside bk.sum(axis) of the same matrix (the same bytes read),
+    var(axis) beside two such sums; and beside its torch counterpart."""
+    bk.init()
+    emit(kernel="device", **bk.device_info())
+    for dtype, esize, shape in (("float64", 8, (10000, 10000)), ("float32", 4, (10000, 10000)),
+                                ("float64", 8, (10**7, 8))):
+        rows, cols = shape
+        n = rows * cols
+        tdt = torch.float64 if dtype == "float64" else torch.float32
+        x = bk.random.uniform(0.0, 1.0, shape, dtype=dtype)._materialize()
+        y = bk.random.uniform(0.0, 1.0, shape, dtype=dtype)._materialize()
+        vc = bk.random.uniform(0.0, 1.0, (cols,), dtype=dtype)._materialize()
+        vr = bk.random.uniform(0.0, 1.0, (rows, 1), dtype=dtype)._materialize()
+        tx = torch.empty(shape, dtype=tdt, device="cuda").uniform_()
+        tvc = torch.empty(cols, dtype=tdt, device="cuda").uniform_()
+        tvr = torch.empty((rows, 1), dtype=tdt, device="cuda").uniform_()
+        tag = f"{dtype} {rows}x{cols}"
+
+        def row(kernel, fn, timer, nbytes, **kw):
+            ms, mn, mx = spread(fn, timer, reps=10, warmup=2)
+            emit(kernel=f"{kernel} [{tag}]", rows=rows, cols=cols, ms=ms, min_ms=mn, max_ms=mx,
+                 GBps=nbytes / ms / 1e6, **kw)
+            return ms, mn, mx
+
+        e_ms, e_mn, e_mx = row("subtract (X - Y, equal shapes)", lambda: bk.subtract(x, y), "bk", 3 * n * esize)
+        for name, v, tv in (("row vector v[c]", vc, tvc), ("column vector v[r]", vr, tvr)):
+            ms, _, _ = row(f"broadcast subtract (X - {name})", lambda: bk.subtract(x, v), "bk", 2 * n * esize)
+            t_ms, _, _ = row(f"torch X - {name}", lambda: tx - tv, "torch", 2 * n * esize)
+            emit(kernel=f"broadcast {name} vs equal-shape subtract [{tag}]", ratio=ms / e_ms,
+                 no_longer_than_subtract=bool(ms <= e_ms), vs_torch=ms / t_ms)
+        for axis in (0, 1):
+            s_ms, s_mn, s_mx = row(f"sum(axis={axis})", lambda: bk.sum(x, axis=axis), "bk", n * esize)
+            ms, _, _ = row(f"max(axis={axis})", lambda: bk.amax(x, axis=axis), "bk", n * esize)
+            t_ms, _, _ = row(f"torch.amax(dim={axis})", lambda: torch.amax(tx, dim=axis), "torch", n * esize)
+            emit(kernel=f"max(axis={axis}) vs sum(axis={axis}) [{tag}]", ratio=ms / s_ms,
+                 within_sum_plus_spread=bool(ms <= s_ms + (s_mx - s_mn)), vs_torch=ms / t_ms)
+            ms, _, _ = row(f"var(axis={axis}) (two passes)", lambda: bk.var(x, axis=axis), "bk", 2 * n * esize)
+            t_ms, _, _ = row(f"torch.var(dim={axis})", lambda: torch.var(tx, dim=axis, unbiased=False), "torch",
+                             2 * n * esize)
+            emit(kernel=f"var(axis={axis}) vs 2 x sum(axis={axis}) [{tag}]", sums=ms / s_ms,
+                 within_two_sums_plus_spread=bool(ms <= 2 * s_ms + (s_mx - s_mn)), vs_torch=ms / t_ms)
+        del x, y, vc, vr, tx, tvc, tvr
+
+
 def emit(**kw):
     print(json.dumps(kw), flush=True)
 
@@ -267,4 +317,5 @@ def main():
 
 
 if __name__ == "__main__":
-    mask_rows() if sys.argv[1:] == ["masks"] else stats_rows() if sys.argv[1:] == ["stats"] else main()
+    modes = {"masks": mask_rows, "stats": stats_rows, "axis": axis_rows}
+    modes[sys.argv[1]]() if len(sys.argv) == 2 and sys.argv[1] in modes else main()
