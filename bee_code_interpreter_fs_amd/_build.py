@@ -56,7 +56,9 @@ def _targets() -> List[Target]:
     # not part of the daemon
     ex_srcs = sorted(os.path.join(ex, f) for f in os.listdir(ex)
                      if f.endswith(".cpp") and f not in ("broker_fuzz.cpp", "admission_test.cpp")) if os.path.isdir(ex) else []
-    ex_hdrs = sorted(os.path.join(ex, f) for f in os.listdir(ex) if f.endswith(".hpp")) if os.path.isdir(ex) else []
+    # (broker.cpp includes the kernel library's interface, "../kernels/beekern.h")
+    ex_hdrs = (sorted(os.path.join(ex, f) for f in os.listdir(ex) if f.endswith(".hpp")) + [os.path.join(k, "beekern.h")]
+               if os.path.isdir(ex) else [])
     rb = os.path.join(CSRC, "rccl_bench")
     targets = [
         Target(
@@ -66,7 +68,7 @@ def _targets() -> List[Target]:
             compiler=HIPCC,
             compile_flags=HIP_FLAGS,
             link_flags=[f"--offload-arch={ARCH}", "-shared", "-fPIC"],
-            headers=[os.path.join(k, f) for f in ("bk_common.hpp", "bk_philox.hpp", "bk_ticket.hpp", "bk_binary_op.hpp", "gemm256_impl.hpp", "gemm256w4_impl.hpp")],
+            headers=[os.path.join(k, f) for f in ("beekern.h", "bk_common.hpp", "bk_philox.hpp", "bk_ticket.hpp", "bk_binary_op.hpp", "gemm256_impl.hpp", "gemm256w4_impl.hpp")],
             hip=True,
         ),
     ]
@@ -84,7 +86,7 @@ def _targets() -> List[Target]:
                 link_flags=["-pthread", f"-L{ROCM}/lib", "-lamdhip64", "-lrocprofiler-sdk-roctx", "-ldl",
                             f"-Wl,-rpath,{ROCM}/lib"],
                 shared=False,
-                headers=sorted(os.path.join(ex, f) for f in os.listdir(ex) if f.endswith(".hpp")),
+                headers=ex_hdrs,
             )
         )
     if os.path.isdir(q) and os.listdir(q):
@@ -176,7 +178,7 @@ def _targets() -> List[Target]:
                 # 256 accumulators + fragments otherwise bounce through AGPR moves
                 compile_flags=HIP_FLAGS + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                 link_flags=[f"--offload-arch={ARCH}", "-shared", "-fPIC"],
-                headers=[os.path.join(k, "bk_common.hpp"), os.path.join(k, "gemm256_impl.hpp"), os.path.join(k, "gemm256w4_impl.hpp")],
+                headers=[os.path.join(k, "beekern.h"), os.path.join(k, "bk_common.hpp"), os.path.join(k, "gemm256_impl.hpp"), os.path.join(k, "gemm256w4_impl.hpp")],
                 hip=True,
                 optional=True,
             )

@@ -61,92 +61,86 @@ def _preload_torch_runtime() -> None:
         pass
 
 
+# name -> (argument types, result type) of every entry point bound here: the Python side's
+# copy of csrc/kernels/beekern.h (tests/test_native_abi_cpu.py checks one against the other)
+c_int, c_i64, c_u64, c_vp, c_d, c_f = (
+    ctypes.c_int,
+    ctypes.c_int64,
+    ctypes.c_uint64,
+    ctypes.c_void_p,
+    ctypes.c_double,
+    ctypes.c_float,
+)
+SIGNATURES = {
+    "bk_version": ([], c_int),
+    "bk_last_error": ([], ctypes.c_char_p),
+    "bk_init": ([c_int], c_int),
+    "bk_device": ([], c_int),
+    "bk_set_quota": ([c_i64], c_int),
+    "bk_quota": ([], c_i64),
+    "bk_malloc": ([ctypes.POINTER(c_vp), c_i64], c_int),
+    "bk_free": ([c_vp], c_int),
+    "bk_empty_cache": ([], c_int),
+    "bk_memory_stats": ([ctypes.POINTER(c_i64)], c_int),
+    "bk_memcpy": ([c_vp, c_vp, c_i64, c_int, c_vp], c_int),
+    "bk_memcpy_async": ([c_vp, c_vp, c_i64, c_int, c_vp], c_int),
+    "bk_sync": ([c_vp], c_int),
+    "bk_preload": ([c_vp], c_int),
+    "bk_workspace_bytes": ([c_int], c_i64),
+    "bk_workspace_init": ([c_int, c_vp, c_vp], c_int),
+    "bk_device_info": ([ctypes.POINTER(c_i64), ctypes.c_char_p, c_int], c_int),
+    "bk_event_pair_create": ([ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)], c_int),
+    "bk_event_record": ([c_vp, c_vp], c_int),
+    "bk_event_elapsed_ms": ([c_vp, c_vp], c_f),
+    "bk_event_destroy": ([c_vp], c_int),
+    "bk_rand_uniform": ([c_vp, c_i64, c_int, c_u64, c_u64, c_d, c_d, c_vp], c_int),
+    "bk_rand_normal": ([c_vp, c_i64, c_int, c_u64, c_u64, c_d, c_d, c_vp], c_int),
+    "bk_unary": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp], c_int),
+    "bk_binary": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_vp, c_i64, c_vp], c_int),
+    "bk_cast": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp], c_int),
+    "bk_fill": ([c_vp, c_i64, c_u64, c_int, c_vp], c_int),
+    "bk_reduce": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp], c_int),
+    "bk_rand_reduce": ([c_int, c_int, c_i64, c_u64, c_u64, c_d, c_d, c_vp, c_vp, c_vp], c_int),
+    "bk_compare": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_vp, c_i64, c_vp], c_int),
+    "bk_compare_count": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_i64, c_vp, c_vp, c_vp], c_int),
+    "bk_mask_logical": ([c_int, c_vp, c_vp, c_vp, c_i64, c_vp], c_int),
+    "bk_where": ([c_int, c_vp, c_int, c_vp, c_vp, c_d, c_d, c_vp, c_i64, c_vp], c_int),
+    "bk_compress": ([c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
+    "bk_select": ([c_int, c_vp, c_i64, ctypes.POINTER(c_i64), c_int, c_vp, c_vp, c_vp], c_int),
+    "bk_histogram_max_bins": ([], c_int),
+    "bk_histogram": ([c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp], c_int),
+    "bk_reduce_axis": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp], c_int),
+    "bk_broadcast": ([c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp], c_int),
+    "bk_axis_stat": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_d, c_vp, c_vp, c_vp], c_int),
+    "bk_gemm_bf16_fast_ok": ([c_int, c_int, c_int, c_int, c_int], c_int),
+    "bk_gemm_bf16_tn": (
+        [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_int, c_vp],
+        c_int,
+    ),
+    "bk_gemm_bf16_tn_variant": (
+        [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_int, c_int, c_vp],
+        c_int,
+    ),
+    "bk_gemm_bf16_pick": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int], c_int),
+    "bk_gemm_bf16_nn": (
+        [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_int, c_vp],
+        c_int,
+    ),
+    "bk_gemm_bf16_nn_ok": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int], c_int),
+    "bk_transpose_bf16": ([c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "bk_transpose_to_bf16": ([c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "bk_transpose": ([c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "bk_gemm_fp": ([c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_vp], c_int),
+    "bk_gemm_f32x6_workspace_bytes": ([c_int, c_int, c_int], c_i64),
+    "bk_gemm_f32x6": (
+        [c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp],
+        c_int,
+    ),
+}
+
+
 def _declare(lib: ctypes.CDLL) -> None:
-    c_int, c_i64, c_u64, c_vp, c_d, c_f = (
-        ctypes.c_int,
-        ctypes.c_int64,
-        ctypes.c_uint64,
-        ctypes.c_void_p,
-        ctypes.c_double,
-        ctypes.c_float,
-    )
-    sig = {
-        "bk_version": ([], c_int),
-        "bk_last_error": ([], ctypes.c_char_p),
-        "bk_init": ([c_int], c_int),
-        "bk_device": ([], c_int),
-        "bk_set_quota": ([c_i64], c_int),
-        "bk_quota": ([], c_i64),
-        "bk_malloc": ([ctypes.POINTER(c_vp), c_i64], c_int),
-        "bk_free": ([c_vp], c_int),
-        "bk_empty_cache": ([], c_int),
-        "bk_memory_stats": ([ctypes.POINTER(c_i64)], c_int),
-        "bk_memcpy": ([c_vp, c_vp, c_i64, c_int, c_vp], c_int),
-        "bk_memcpy_async": ([c_vp, c_vp, c_i64, c_int, c_vp], c_int),
-        "bk_sync": ([c_vp], c_int),
-        "bk_preload": ([c_vp], c_int),
-        "bk_device_info": ([ctypes.POINTER(c_i64), ctypes.c_char_p, c_int], c_int),
-        "bk_event_pair_create": ([ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)], c_int),
-        "bk_event_record": ([c_vp, c_vp], c_int),
-        "bk_event_elapsed_ms": ([c_vp, c_vp], c_f),
-        "bk_event_destroy": ([c_vp], c_int),
-        "bk_rand_uniform": ([c_vp, c_i64, c_int, c_u64, c_u64, c_d, c_d, c_vp], c_int),
-        "bk_rand_normal": ([c_vp, c_i64, c_int, c_u64, c_u64, c_d, c_d, c_vp], c_int),
-        "bk_unary": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp], c_int),
-        "bk_binary": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_vp, c_i64, c_vp], c_int),
-        "bk_cast": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp], c_int),
-        "bk_fill": ([c_vp, c_i64, c_u64, c_int, c_vp], c_int),
-        "bk_reduce_workspace_bytes": ([], c_int),
-        "bk_reduce": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp], c_int),
-        "bk_rand_reduce": ([c_int, c_int, c_i64, c_u64, c_u64, c_d, c_d, c_vp, c_vp, c_vp], c_int),
-        "bk_compare": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_vp, c_i64, c_vp], c_int),
-        "bk_compare_count": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_i64, c_vp, c_vp, c_vp], c_int),
-        "bk_mask_logical": ([c_int, c_vp, c_vp, c_vp, c_i64, c_vp], c_int),
-        "bk_where": ([c_int, c_vp, c_int, c_vp, c_vp, c_d, c_d, c_vp, c_i64, c_vp], c_int),
-        "bk_compress_workspace_bytes": ([], c_i64),
-        "bk_compress_workspace_init": ([c_vp, c_vp], c_int),
-        "bk_compress": ([c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
-        "bk_select_workspace_bytes": ([], c_i64),
-        "bk_select_workspace_init": ([c_vp, c_vp], c_int),
-        "bk_select": ([c_int, c_vp, c_i64, ctypes.POINTER(c_i64), c_int, c_vp, c_vp, c_vp], c_int),
-        "bk_histogram_max_bins": ([], c_int),
-        "bk_histogram_workspace_bytes": ([], c_i64),
-        "bk_histogram_workspace_init": ([c_vp, c_vp], c_int),
-        "bk_histogram": ([c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp], c_int),
-        "bk_reduce_axis_workspace_bytes": ([], c_i64),
-        "bk_reduce_workspace_init": ([c_vp, c_vp], c_int),
-        "bk_reduce_axis_workspace_init": ([c_vp, c_vp], c_int),
-        "bk_reduce_axis": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp], c_int),
-        "bk_broadcast": ([c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp], c_int),
-        "bk_axis_stat_workspace_bytes": ([], c_i64),
-        "bk_axis_stat_workspace_init": ([c_vp, c_vp], c_int),
-        "bk_axis_stat": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_d, c_vp, c_vp, c_vp], c_int),
-        "bk_gemm_bf16_fast_ok": ([c_int, c_int, c_int, c_int, c_int], c_int),
-        "bk_gemm_bf16_tn": (
-            [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_int, c_vp],
-            c_int,
-        ),
-        "bk_gemm_bf16_tn_variant": (
-            [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_int, c_int, c_vp],
-            c_int,
-        ),
-        "bk_gemm_bf16_pick": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int], c_int),
-        "bk_gemm_bf16_nn": (
-            [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_int, c_vp],
-            c_int,
-        ),
-        "bk_gemm_bf16_nn_ok": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int], c_int),
-        "bk_transpose_bf16": ([c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),
-        "bk_transpose_to_bf16": ([c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),
-        "bk_transpose": ([c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),
-        "bk_gemm_fp": ([c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_vp], c_int),
-        "bk_gemm_f32x6_workspace_bytes": ([c_int, c_int, c_int], c_i64),
-        "bk_gemm_f32x6": (
-            [c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp],
-            c_int,
-        ),
-    }
-    for name, (args, res) in sig.items():
+    for name, (args, res) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

@@ -760,7 +760,7 @@ def max_abs_diff(a, b) -> np.float64:
 # ---- per-axis max / min / var / std (csrc/kernels/axis.hip) --------------------------
 
 _STAT = {"max": 0, "min": 1, "var": 2, "std": 3}
-MAX_AXIS0_COLUMNS = 1 << 18  # = kWsDoubles (axis.hip): the column form's workspace
+MAX_AXIS0_COLUMNS = 1 << 18  # = BK_MAX_AXIS0_COLUMNS (csrc/kernels/beekern.h): the column form's workspace
 
 
 def _stat_axis(what: str, x: DeviceArray, axis) -> Optional[int]:
@@ -1066,7 +1066,7 @@ def where(mask, a, b, dtype=None) -> DeviceArray:
 # ---- order statistics and histograms (csrc/kernels/stats.hip) ------------------------
 
 _SELECT_Q = 16  # quantiles per select call: two neighbouring ranks each, 32 ranks a call
-MAX_HISTOGRAM_BINS = 4096  # = kMaxBins (stats.hip), driver.MAX_BINS
+MAX_HISTOGRAM_BINS = 4096  # = BK_MAX_BINS (csrc/kernels/beekern.h), driver.MAX_BINS
 
 
 def _stats_operand(what: str, x) -> DeviceArray:

@@ -32,12 +32,15 @@ _vp = ctypes.c_void_p
 
 
 # bk_select takes 1 to MAX_RANKS ranks a call, bk_histogram 1 to MAX_BINS bins
-# (kMaxRanks / kMaxBins of csrc/kernels/stats.hip and the broker's checks)
+# (BK_MAX_RANKS / BK_MAX_BINS of csrc/kernels/beekern.h and the broker's checks)
 MAX_RANKS = 32
 MAX_BINS = 4096
 _STATS_EDGES_AT = 512
 _STATS_COUNTS_AT = _STATS_EDGES_AT + (MAX_BINS + 1) * 8
 _STATS_SCRATCH_BYTES = _STATS_COUNTS_AT + MAX_BINS * 8
+
+# the kernels' scratch workspaces: enum BkWorkspace of csrc/kernels/beekern.h
+WS_REDUCE, WS_REDUCE_AXIS, WS_AXIS_STAT, WS_COMPRESS, WS_SELECT, WS_HISTOGRAM, WS_COUNT = range(7)
 
 
 class NativeDriver:
@@ -47,21 +50,24 @@ class NativeDriver:
         self.lib = _native.lib()
         self.stream = _vp(0)
         self.device: Optional[int] = None
-        self.ws = 0
+        self.workspaces = [0] * WS_COUNT  # by kind
         self.scalar = 0
-        self.axis_ws = 0
-        self.axis_stat_ws = 0
-        self.compress_ws = 0
-        self.select_ws = 0
-        self.hist_ws = 0
         self.stats_scratch = 0
 
     def init(self, device: int) -> None:
         check(self.lib.bk_init(int(device)), "bk_init")
         self.device = device
-        self.ws = self.malloc(self.lib.bk_reduce_workspace_bytes())
-        check(self.lib.bk_reduce_workspace_init(_vp(self.ws), self.stream), "bk_reduce_workspace_init")
+        self._workspace(WS_REDUCE)  # (the reductions read workspaces[WS_REDUCE] themselves)
         self.scalar = self.malloc(256)
+
+    def _workspace(self, kind: int) -> int:
+        """The workspace of ``kind``, allocated and initialised on first use."""
+        ws = self.workspaces[kind]
+        if not ws:
+            ws = self.malloc(self.lib.bk_workspace_bytes(kind))
+            check(self.lib.bk_workspace_init(kind, _vp(ws), self.stream), "bk_workspace_init")
+            self.workspaces[kind] = ws
+        return ws
 
     def malloc(self, nbytes: int) -> int:
         out = _vp()
@@ -96,14 +102,15 @@ class NativeDriver:
         check(self.lib.bk_fill(_vp(y), nbytes, pattern, width, self.stream), "bk_fill")
 
     def reduce(self, op: int, dt: int, a: int, b: int, n: int) -> float:
-        check(self.lib.bk_reduce(op, dt, _vp(a), _vp(b) if b else None, n, _vp(self.ws), _vp(self.scalar), self.stream), "bk_reduce")
+        check(self.lib.bk_reduce(op, dt, _vp(a), _vp(b) if b else None, n, _vp(self.workspaces[WS_REDUCE]),
+                                 _vp(self.scalar), self.stream), "bk_reduce")
         out = np.zeros(1, np.float64)
         self.d2h(self.scalar, out)
         return float(out[0])
 
     def rand_reduce(self, op: int, dt: int, n: int, seed: int, off: int, lo: float, hi: float) -> float:
-        check(self.lib.bk_rand_reduce(op, dt, n, seed & 0xFFFFFFFFFFFFFFFF, off, lo, hi, _vp(self.ws), _vp(self.scalar),
-                                      self.stream), "bk_rand_reduce")
+        check(self.lib.bk_rand_reduce(op, dt, n, seed & 0xFFFFFFFFFFFFFFFF, off, lo, hi, _vp(self.workspaces[WS_REDUCE]),
+                                      _vp(self.scalar), self.stream), "bk_rand_reduce")
         out = np.zeros(1, np.float64)
         self.d2h(self.scalar, out)
         return float(out[0])
@@ -134,11 +141,8 @@ class NativeDriver:
                                      self.stream), "bk_gemm_f32x6")
 
     def reduce_axis(self, op: int, dt: int, x: int, y: int, rows: int, cols: int, ld: int, axis: int) -> None:
-        if not self.axis_ws:
-            self.axis_ws = self.malloc(self.lib.bk_reduce_axis_workspace_bytes())
-            check(self.lib.bk_reduce_axis_workspace_init(_vp(self.axis_ws), self.stream), "bk_reduce_axis_workspace_init")
-        check(self.lib.bk_reduce_axis(op, dt, _vp(x), rows, cols, ld, axis, _vp(y), _vp(self.axis_ws), self.stream),
-              "bk_reduce_axis")
+        check(self.lib.bk_reduce_axis(op, dt, _vp(x), rows, cols, ld, axis, _vp(y), _vp(self._workspace(WS_REDUCE_AXIS)),
+                                      self.stream), "bk_reduce_axis")
 
     # ---- a matrix against a vector, per-axis statistics (csrc/kernels/axis.hip) -------
     def broadcast(self, op: int, dt: int, kind: int, swapped: bool, a: int, v: int, y: int, rows: int, cols: int,
@@ -152,12 +156,8 @@ class NativeDriver:
                   divisor: float) -> None:
         """y = max (op 0) / min (1) / var (2) / std (3) of x[rows, cols] along ``axis``, in x's
         dtype (f32 / f64); divisor: the variance's n - ddof."""
-        if not self.axis_stat_ws:
-            self.axis_stat_ws = self.malloc(self.lib.bk_axis_stat_workspace_bytes())
-            check(self.lib.bk_axis_stat_workspace_init(_vp(self.axis_stat_ws), self.stream),
-                  "bk_axis_stat_workspace_init")
         check(self.lib.bk_axis_stat(op, dt, _vp(x), rows, cols, ld, axis, float(divisor), _vp(y),
-                                    _vp(self.axis_stat_ws), self.stream), "bk_axis_stat")
+                                    _vp(self._workspace(WS_AXIS_STAT)), self.stream), "bk_axis_stat")
 
     # ---- boolean masks (csrc/kernels/mask.hip): one byte per element ----------------
     def compare(self, op: int, dt: int, mode: int, a: int, b: int, sc: float, y: int, n: int) -> None:
@@ -166,7 +166,7 @@ class NativeDriver:
 
     def compare_count(self, op: int, dt: int, mode: int, a: int, b: int, sc: float, n: int) -> float:
         """The number of true comparisons, no mask written (one fused launch)."""
-        check(self.lib.bk_compare_count(op, dt, mode, _vp(a), _vp(b) if b else None, sc, n, _vp(self.ws),
+        check(self.lib.bk_compare_count(op, dt, mode, _vp(a), _vp(b) if b else None, sc, n, _vp(self.workspaces[WS_REDUCE]),
                                         _vp(self.scalar), self.stream), "bk_compare_count")
         out = np.zeros(1, np.float64)
         self.d2h(self.scalar, out)
@@ -183,10 +183,7 @@ class NativeDriver:
 
     def compress(self, dt: int, x: int, mask: int, n: int, y: int, cap: int) -> None:
         """y[0:cap] = x[mask] in index order (writes past cap are dropped)."""
-        if not self.compress_ws:
-            self.compress_ws = self.malloc(self.lib.bk_compress_workspace_bytes())
-            check(self.lib.bk_compress_workspace_init(_vp(self.compress_ws), self.stream), "bk_compress_workspace_init")
-        check(self.lib.bk_compress(dt, _vp(x), _vp(mask), n, _vp(y), cap, _vp(self.compress_ws), self.stream),
+        check(self.lib.bk_compress(dt, _vp(x), _vp(mask), n, _vp(y), cap, _vp(self._workspace(WS_COMPRESS)), self.stream),
               "bk_compress")
 
     # ---- order statistics and histograms (csrc/kernels/stats.hip) ---------------------
@@ -201,12 +198,9 @@ class NativeDriver:
         """(np.sort(x)[k] as a float for every 0-based k of ``ranks`` (1 to
         32 of them), the number of NaNs in x); x is only read."""
         ranks = [int(k) for k in ranks]
-        if not self.select_ws:
-            self.select_ws = self.malloc(self.lib.bk_select_workspace_bytes())
-            check(self.lib.bk_select_workspace_init(_vp(self.select_ws), self.stream), "bk_select_workspace_init")
         out = self._stats_scratch()
         karr = (ctypes.c_int64 * max(len(ranks), 1))(*ranks)
-        check(self.lib.bk_select(dt, _vp(x), n, karr, len(ranks), _vp(out), _vp(self.select_ws), self.stream),
+        check(self.lib.bk_select(dt, _vp(x), n, karr, len(ranks), _vp(out), _vp(self._workspace(WS_SELECT)), self.stream),
               "bk_select")
         host = np.zeros(len(ranks) + 1, np.float64)
         self.d2h(out, host)
@@ -219,14 +213,11 @@ class NativeDriver:
         bins = edges.size - 1
         if not 1 <= bins <= MAX_BINS:
             raise BeekernError(f"bk_histogram: 1 to {MAX_BINS} bins, got {bins}")
-        if not self.hist_ws:
-            self.hist_ws = self.malloc(self.lib.bk_histogram_workspace_bytes())
-            check(self.lib.bk_histogram_workspace_init(_vp(self.hist_ws), self.stream), "bk_histogram_workspace_init")
         base = self._stats_scratch()
         d_edges, d_counts = base + _STATS_EDGES_AT, base + _STATS_COUNTS_AT
         self.h2d(d_edges, edges)
-        check(self.lib.bk_histogram(dt, _vp(x), n, _vp(d_edges), bins, _vp(d_counts), _vp(self.hist_ws), self.stream),
-              "bk_histogram")
+        check(self.lib.bk_histogram(dt, _vp(x), n, _vp(d_edges), bins, _vp(d_counts), _vp(self._workspace(WS_HISTOGRAM)),
+                                    self.stream), "bk_histogram")
         counts = np.zeros(bins, np.uint64)
         self.d2h(d_counts, counts)
         return counts.astype(np.int64)

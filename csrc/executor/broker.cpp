@@ -14,9 +14,14 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../kernels/beekern.h"
 #include "util.hpp"
 
 namespace bee {
+
+// (broker_core.hpp stays HIP-free and keeps its own copies of the limits)
+static_assert(broker::kMaxBins == BK_MAX_BINS && broker::kMaxRanks == BK_MAX_RANKS,
+              "broker_core.hpp and csrc/kernels/beekern.h disagree on a limit");
 
 namespace {
 
@@ -40,55 +45,20 @@ bool sym(void* lib, const char* name, F* out) {
 
 class HipDevice final : public broker::Device {
  public:
-  // beekern entry points (csrc/kernels), resolved from libbeekern.so
+  // beekern entry points (csrc/kernels), resolved from libbeekern.so: typed
+  // by their declarations in beekern.h, every one required by load()
+#define BEE_BK_ENTRY_POINTS(X)                                                                                       \
+  X(init) X(last_error) X(set_quota) X(malloc) X(free) X(reserve) X(preload) X(workspace_bytes) X(workspace_init)     \
+  X(rand_uniform) X(rand_normal) X(unary) X(binary) X(cast) X(fill) X(reduce) X(rand_reduce) X(reduce_axis)          \
+  X(gemm_bf16_tn) X(gemm_bf16_nn) X(gemm_fp) X(gemm_f32x6) X(transpose)                                              \
+  X(compare) X(compare_count) X(mask_logical) X(where) X(compress) /* boolean masks (mask.hip) */                    \
+  X(select) X(histogram)                                           /* order statistics, histograms (stats.hip) */    \
+  X(broadcast) X(axis_stat)                                        /* matrix against vector, axis statistics (axis.hip) */
   struct Bk {
-    int (*init)(int);
-    const char* (*last_error)();
-    int (*set_quota)(int64_t);
-    int (*malloc_)(void**, int64_t);
-    int (*free_)(void*);
-    int (*rand_uniform)(void*, int64_t, int, uint64_t, uint64_t, double, double, hipStream_t);
-    int (*rand_normal)(void*, int64_t, int, uint64_t, uint64_t, double, double, hipStream_t);
-    int (*unary)(int, int, const void*, void*, int64_t, hipStream_t);
-    int (*binary)(int, int, int, const void*, const void*, double, void*, int64_t, hipStream_t);
-    int (*cast)(int, int, const void*, void*, int64_t, hipStream_t);
-    int (*fill)(void*, int64_t, uint64_t, int, hipStream_t);
-    int (*reduce_ws)();
-    int (*rand_reduce)(int, int, int64_t, uint64_t, uint64_t, double, double, void*, void*, hipStream_t);
-    int (*reduce)(int, int, const void*, const void*, int64_t, void*, void*, hipStream_t);
-    int (*gemm)(const void*, const void*, void*, int, int, int, int, int, int, float, float, int, hipStream_t);
-    int (*gemm_nn)(const void*, const void*, void*, int, int, int, int, int, int, float, float, int, hipStream_t);
-    int (*transpose)(int, int, const void*, void*, int, int, int, int, hipStream_t);
-    int (*preload)(hipStream_t);
-    int (*reserve)(int64_t);
-    int64_t (*axis_ws)();
-    int (*ws_init)(void*, hipStream_t);       // zero a fresh workspace's completion tickets
-    int (*axis_ws_init)(void*, hipStream_t);
-    int (*reduce_axis)(int, int, const void*, int64_t, int64_t, int64_t, int, void*, void*, hipStream_t);
-    int (*gemm_fp)(int, int, int, const void*, const void*, void*, int, int, int, int64_t, int64_t, int64_t, hipStream_t);
-    int (*gemm_f32x6)(int, int, const void*, const void*, void*, int, int, int, int64_t, int64_t, int64_t, void*, int64_t,
-                      hipStream_t);
-    // boolean masks (csrc/kernels/mask.hip)
-    int (*compare)(int, int, int, const void*, const void*, double, void*, int64_t, hipStream_t);
-    int (*compare_count)(int, int, int, const void*, const void*, double, int64_t, void*, void*, hipStream_t);
-    int (*mask_logical)(int, const void*, const void*, void*, int64_t, hipStream_t);
-    int (*where)(int, const void*, int, const void*, const void*, double, double, void*, int64_t, hipStream_t);
-    int64_t (*compress_ws)();
-    int (*compress_ws_init)(void*, hipStream_t);
-    int (*compress)(int, const void*, const void*, int64_t, void*, int64_t, void*, hipStream_t);
-    // order statistics and histograms (csrc/kernels/stats.hip)
-    int64_t (*select_ws)();
-    int (*select_ws_init)(void*, hipStream_t);
-    int (*select)(int, const void*, int64_t, const int64_t*, int, void*, void*, hipStream_t);
-    int64_t (*hist_ws)();
-    int (*hist_ws_init)(void*, hipStream_t);
-    int (*histogram)(int, const void*, int64_t, const void*, int, void*, void*, hipStream_t);
-    // a matrix against a vector, per-axis statistics (csrc/kernels/axis.hip)
-    int (*broadcast)(int, int, int, int, const void*, int64_t, int64_t, int64_t, const void*, void*, int64_t, hipStream_t);
-    int64_t (*axis_stat_ws)();
-    int (*axis_stat_ws_init)(void*, hipStream_t);
-    int (*axis_stat)(int, int, const void*, int64_t, int64_t, int64_t, int, double, void*, void*, hipStream_t);
-  } bk{};
+#define X(name) decltype(&bk_##name) name = nullptr;
+    BEE_BK_ENTRY_POINTS(X)
+#undef X
+  } bk;
 
   // Per-session GPU resources, pooled across sessions: a stream, the
   // reduction workspace and the result slot.  Reductions write their scalar
@@ -99,16 +69,13 @@ class HipDevice final : public broker::Device {
     hipStream_t lo = nullptr;  // normal priority: GEMMs, large draws and passes
     hipStream_t hi = nullptr;  // high priority: the short dependent ops (reductions, casts, GEMV), or null
     hipEvent_t hop = nullptr;  // orders the two streams when an op moves from one to the other
-    void* ws = nullptr;
+    // the kernels' scratch workspaces by kind: the reductions' from the
+    // start, the others allocated on first use (workspace())
+    void* ws[BK_WS_COUNT] = {};
     void* scalar = nullptr;  // device fallback when no pinned slot exists
     double* slot = nullptr;
-    void* axis_ws = nullptr;  // axis-reduction partials, allocated on first use
-    void* compress_ws = nullptr;  // compaction counts and offsets, allocated on first use
-    void* axis_stat_ws = nullptr;  // bk_axis_stat's partials, column means and tickets, allocated on first use
-    // bk_select / bk_histogram: workspaces, and the scratch their results, edges
-    // and counts pass through (kStats*), allocated on first use
-    void* select_ws = nullptr;
-    void* hist_ws = nullptr;
+    // bk_select / bk_histogram: the scratch their results, edges and counts
+    // pass through (kStats*), allocated on first use
     char* stats = nullptr;
     // frees waiting for the stream work recorded before them (event, buffer)
     std::vector<std::pair<hipEvent_t, void*>> pending;
@@ -289,7 +256,7 @@ class HipDevice final : public broker::Device {
     for (size_t i = 0; i < c->pending.size(); ++i) {
       auto& pe = c->pending[i];
       if (all || hipEventQuery(pe.first) == hipSuccess) {
-        bk.free_(pe.second);
+        bk.free(pe.second);
         c->spare_events.push_back(pe.first);
       } else {
         c->pending[keep++] = pe;
@@ -304,46 +271,14 @@ class HipDevice final : public broker::Device {
       *err = std::string("dlopen ") + path + ": " + dlerror();
       return false;
     }
-    const bool ok = sym(lib_, "bk_init", &bk.init) && sym(lib_, "bk_last_error", &bk.last_error) &&
-                    sym(lib_, "bk_set_quota", &bk.set_quota) && sym(lib_, "bk_malloc", &bk.malloc_) &&
-                    sym(lib_, "bk_free", &bk.free_) && sym(lib_, "bk_rand_uniform", &bk.rand_uniform) &&
-                    sym(lib_, "bk_rand_normal", &bk.rand_normal) && sym(lib_, "bk_unary", &bk.unary) &&
-                    sym(lib_, "bk_binary", &bk.binary) && sym(lib_, "bk_cast", &bk.cast) &&
-                    sym(lib_, "bk_fill", &bk.fill) && sym(lib_, "bk_reduce_workspace_bytes", &bk.reduce_ws) &&
-                    sym(lib_, "bk_reduce", &bk.reduce) && sym(lib_, "bk_gemm_bf16_tn", &bk.gemm) &&
-                    sym(lib_, "bk_transpose", &bk.transpose) && sym(lib_, "bk_rand_reduce", &bk.rand_reduce);
-    if (!ok) {
-      *err = "libbeekern.so is missing broker entry points";
-      return false;
-    }
-    sym(lib_, "bk_preload", &bk.preload);
-    sym(lib_, "bk_reserve", &bk.reserve);
-    sym(lib_, "bk_reduce_axis_workspace_bytes", &bk.axis_ws);
-    if (!sym(lib_, "bk_reduce_workspace_init", &bk.ws_init) || !sym(lib_, "bk_reduce_axis_workspace_init", &bk.axis_ws_init)) {
-      *err = "libbeekern.so has no reduction workspace init (stale build)";
-      return false;
-    }
-    sym(lib_, "bk_reduce_axis", &bk.reduce_axis);
-    sym(lib_, "bk_gemm_bf16_nn", &bk.gemm_nn);
-    sym(lib_, "bk_gemm_fp", &bk.gemm_fp);
-    sym(lib_, "bk_gemm_f32x6", &bk.gemm_f32x6);
-    sym(lib_, "bk_compare", &bk.compare);
-    sym(lib_, "bk_compare_count", &bk.compare_count);
-    sym(lib_, "bk_mask_logical", &bk.mask_logical);
-    sym(lib_, "bk_where", &bk.where);
-    if (!sym(lib_, "bk_compress_workspace_bytes", &bk.compress_ws) ||
-        !sym(lib_, "bk_compress_workspace_init", &bk.compress_ws_init) || !sym(lib_, "bk_compress", &bk.compress))
-      bk.compress = nullptr;
-    if (!sym(lib_, "bk_select_workspace_bytes", &bk.select_ws) ||
-        !sym(lib_, "bk_select_workspace_init", &bk.select_ws_init) || !sym(lib_, "bk_select", &bk.select))
-      bk.select = nullptr;
-    if (!sym(lib_, "bk_histogram_workspace_bytes", &bk.hist_ws) ||
-        !sym(lib_, "bk_histogram_workspace_init", &bk.hist_ws_init) || !sym(lib_, "bk_histogram", &bk.histogram))
-      bk.histogram = nullptr;
-    sym(lib_, "bk_broadcast", &bk.broadcast);
-    if (!sym(lib_, "bk_axis_stat_workspace_bytes", &bk.axis_stat_ws) ||
-        !sym(lib_, "bk_axis_stat_workspace_init", &bk.axis_stat_ws_init) || !sym(lib_, "bk_axis_stat", &bk.axis_stat))
-      bk.axis_stat = nullptr;
+#define X(name)                                         \
+  if (!sym(lib_, "bk_" #name, &bk.name)) {              \
+    *err = "libbeekern.so has no bk_" #name;            \
+    return false;                                       \
+  }
+    BEE_BK_ENTRY_POINTS(X)
+#undef X
+#undef BEE_BK_ENTRY_POINTS
     return true;
   }
 
@@ -364,7 +299,7 @@ class HipDevice final : public broker::Device {
       return false;
     }
     bk.set_quota(0);  // quotas are enforced per sandbox by the sessions
-    if (bk.reserve) {
+    {
       // large blocks come from segments from now on; the first one now, so a
       // freshly started broker serves its first requests without hipMallocs
       // (BEE_BROKER_RESERVE_BYTES, default 8 GiB of the GPU's 288)
@@ -374,7 +309,7 @@ class HipDevice final : public broker::Device {
       if (bk.reserve(bytes) != 0) BEE_WARN("broker: reserving %lld bytes failed: %s", (long long)bytes, bk.last_error());
       else BEE_INFO("kernel broker: %lld MiB reserved in %.0f ms", (long long)(bytes >> 20), mono_ms() - tr);
     }
-    if (bk.preload) {  // every kernel module now, not on a sandbox's first request
+    {  // every kernel module now, not on a sandbox's first request
       const double tp = mono_ms();
       const int rc = bk.preload(nullptr);
       if (rc != 0) BEE_WARN("bk_preload failed (%d): %s", rc, bk.last_error());
@@ -419,9 +354,8 @@ class HipDevice final : public broker::Device {
         c->hi = nullptr;
       }
     }
-    bk.malloc_(&c->ws, bk.reduce_ws());
-    bk.ws_init(c->ws, c->s);  // (ordered before every reduction on this stream)
-    bk.malloc_(&c->scalar, 256);
+    workspace(c, BK_WS_REDUCE);  // (initialised on c->s: ordered before every reduction on this stream)
+    bk.malloc(&c->scalar, 256);
     void* page = nullptr;
     if (hipHostMalloc(&page, 64, hipHostMallocCoherent) == hipSuccess) c->slot = (double*)page;
     hipEventCreateWithFlags(&c->wait_ev, timing_ ? hipEventDefault : hipEventDisableTiming);
@@ -449,18 +383,31 @@ class HipDevice final : public broker::Device {
       c->spare_events.pop_back();
     } else if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
       hipStreamSynchronize(c->s);
-      bk.free_(p);
+      bk.free(p);
       return;
     }
     if (hipEventRecord(ev, c->s) != hipSuccess) {
       c->spare_events.push_back(ev);
       hipStreamSynchronize(c->s);
-      bk.free_(p);
+      bk.free(p);
       return;
     }
     c->pending.emplace_back(ev, p);
   }
   static hipStream_t st(void* p) { return ((Ctx*)p)->s; }
+
+  // The session's workspace of `kind` (enum BkWorkspace), allocated and
+  // initialised on first use; null if the allocation fails.  The init is
+  // queued on c->s, the session's latest stream: pick() orders a later hop to
+  // the other stream after it.
+  void* workspace(Ctx* c, int kind) {
+    void*& ws = c->ws[kind];
+    if (!ws) {
+      if (bk.malloc(&ws, bk.workspace_bytes(kind)) != 0) return ws = nullptr;
+      bk.workspace_init(kind, ws, c->s);
+    }
+    return ws;
+  }
 
   // The stream for the session's next op.  Short ops -- reductions, casts,
   // small passes, GEMV-sized products -- go to the high-priority stream, so
@@ -487,8 +434,8 @@ class HipDevice final : public broker::Device {
   static bool short_bytes(int64_t n, int64_t elem, int operands = 1) { return n * elem * operands <= kShortBytes; }
   static int64_t elem_bytes(uint32_t dt) { return dt == 1 ? 8 : dt == 2 ? 2 : 4; }
 
-  int malloc(void** p, uint64_t n) override { return bk.malloc_(p, (int64_t)n); }
-  void free(void* p) override { bk.free_(p); }
+  int malloc(void** p, uint64_t n) override { return bk.malloc(p, (int64_t)n); }
+  void free(void* p) override { bk.free(p); }
   bool zero_async(void* p, uint64_t n, void* s) override {
     return timed(s, st(s), [&](hipStream_t q) { return hipMemsetAsync(p, 0, n, q) == hipSuccess ? 0 : 1; }) == 0;
   }
@@ -538,7 +485,7 @@ class HipDevice final : public broker::Device {
   int reduce(uint32_t op, uint32_t dt, const void* a, const void* b, int64_t n, double* out, void* s) override {
     Ctx* c = (Ctx*)s;
     const int rc = timed(s, pick(s, short_bytes(n, elem_bytes(dt), b ? 2 : 1)), [&](hipStream_t q) {
-      return bk.reduce((int)op, (int)dt, a, b, n, c->ws, c->slot ? (void*)c->slot : c->scalar, q);
+      return bk.reduce((int)op, (int)dt, a, b, n, c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
     });
     return fetch(c, rc, out);
   }
@@ -547,30 +494,27 @@ class HipDevice final : public broker::Device {
     Ctx* c = (Ctx*)s;
     // (compute-bound: ~4 us per 4M values)
     const int rc = timed(s, pick(s, n <= (1ll << 22)), [&](hipStream_t q) {
-      return bk.rand_reduce((int)op, (int)dt, n, seed, off, lo, hi, c->ws, c->slot ? (void*)c->slot : c->scalar, q);
+      return bk.rand_reduce((int)op, (int)dt, n, seed, off, lo, hi, c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
     });
     return fetch(c, rc, out);
   }
   int gemm(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc, float alpha,
            float beta, int odt, void* s) override {
     return timed(s, pick(s, short_gemm(M, N, K)),
-                 [&](hipStream_t q) { return bk.gemm(A, Bt, C, M, N, K, lda, ldb, ldc, alpha, beta, odt, q); });
+                 [&](hipStream_t q) { return bk.gemm_bf16_tn(A, Bt, C, M, N, K, lda, ldb, ldc, alpha, beta, odt, q); });
   }
   int gemm_nn(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, float alpha,
               float beta, int odt, void* s) override {
-    if (!bk.gemm_nn) return broker::kBadArgument;
     return timed(s, pick(s, short_gemm(M, N, K)),
-                 [&](hipStream_t q) { return bk.gemm_nn(A, B, C, M, N, K, lda, ldb, ldc, alpha, beta, odt, q); });
+                 [&](hipStream_t q) { return bk.gemm_bf16_nn(A, B, C, M, N, K, lda, ldb, ldc, alpha, beta, odt, q); });
   }
   int gemm_fp(uint32_t dt, bool ta, bool tb, const void* A, const void* B, void* C, int M, int N, int K, int64_t lda,
               int64_t ldb, int64_t ldc, void* s) override {
-    if (!bk.gemm_fp) return broker::kBadArgument;
     return timed(s, pick(s, short_gemm(M, N, K)),
                  [&](hipStream_t q) { return bk.gemm_fp((int)dt, ta, tb, A, B, C, M, N, K, lda, ldb, ldc, q); });
   }
   int gemm_f32x6(bool ta, bool tb, const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb,
                  int64_t ldc, void* ws, uint64_t ws_bytes, void* s) override {
-    if (!bk.gemm_f32x6) return broker::kBadArgument;
     return timed(s, pick(s, short_gemm(M, N, K)), [&](hipStream_t q) {
       return bk.gemm_f32x6(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, ws, (int64_t)ws_bytes, q);
     });
@@ -581,93 +525,73 @@ class HipDevice final : public broker::Device {
   }
   int reduce_axis(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,
                   uint32_t axis, void* s) override {
-    Ctx* c = (Ctx*)s;
-    if (!bk.reduce_axis || !bk.axis_ws) return broker::kBadArgument;
-    if (!c->axis_ws) {
-      if (bk.malloc_(&c->axis_ws, bk.axis_ws()) != 0) return broker::kOutOfMemory;
-      bk.axis_ws_init(c->axis_ws, c->s);
-    }
+    void* ws = workspace((Ctx*)s, BK_WS_REDUCE_AXIS);
+    if (!ws) return broker::kOutOfMemory;
     // a row / column sum reads the matrix once: ~64 MiB at 4096^2 f32 is
     // ~10 us -- short next to the GEMM that produced it
     return timed(s, pick(s, short_bytes(rows * ld, elem_bytes(dt)) || rows * ld <= (16ll << 20)),
-                 [&](hipStream_t q) { return bk.reduce_axis((int)op, (int)dt, x, rows, cols, ld, (int)axis, y, c->axis_ws, q); });
+                 [&](hipStream_t q) { return bk.reduce_axis((int)op, (int)dt, x, rows, cols, ld, (int)axis, y, ws, q); });
   }
   int broadcast(uint32_t op, uint32_t dt, uint32_t kind, bool swapped, const void* a, const void* v, void* y,
                 int64_t rows, int64_t cols, int64_t lda, int64_t ldy, void* s) override {
-    if (!bk.broadcast) return broker::kBadArgument;
     return timed(s, pick(s, short_bytes(rows * cols, elem_bytes(dt), 2)), [&](hipStream_t q) {
       return bk.broadcast((int)op, (int)dt, (int)kind, swapped ? 1 : 0, a, rows, cols, lda, v, y, ldy, q);
     });
   }
   int axis_stat(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld, uint32_t axis,
                 double divisor, void* s) override {
-    Ctx* c = (Ctx*)s;
-    if (!bk.axis_stat) return broker::kBadArgument;
-    if (!c->axis_stat_ws) {
-      if (bk.malloc_(&c->axis_stat_ws, bk.axis_stat_ws()) != 0) return broker::kOutOfMemory;
-      bk.axis_stat_ws_init(c->axis_stat_ws, c->s);
-    }
+    void* ws = workspace((Ctx*)s, BK_WS_AXIS_STAT);
+    if (!ws) return broker::kOutOfMemory;
     // (the variance reads the matrix twice)
     return timed(s, pick(s, short_bytes(rows * cols, elem_bytes(dt), op >= 2 ? 2 : 1)), [&](hipStream_t q) {
-      return bk.axis_stat((int)op, (int)dt, x, rows, cols, ld, (int)axis, divisor, y, c->axis_stat_ws, q);
+      return bk.axis_stat((int)op, (int)dt, x, rows, cols, ld, (int)axis, divisor, y, ws, q);
     });
   }
   // boolean masks: a mask is one byte per element
   int compare(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double sc, void* y, int64_t n,
               void* s) override {
-    if (!bk.compare) return broker::kBadArgument;
     return timed(s, pick(s, short_bytes(n, elem_bytes(dt) * (mode == 0 ? 2 : 1) + 1)),
                  [&](hipStream_t q) { return bk.compare((int)op, (int)dt, (int)mode, a, b, sc, y, n, q); });
   }
   int compare_count(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double sc, int64_t n,
                     double* out, void* s) override {
-    if (!bk.compare_count) return broker::kBadArgument;
     Ctx* c = (Ctx*)s;
     const int rc = timed(s, pick(s, short_bytes(n, elem_bytes(dt), mode == 0 ? 2 : 1)), [&](hipStream_t q) {
-      return bk.compare_count((int)op, (int)dt, (int)mode, a, b, sc, n, c->ws, c->slot ? (void*)c->slot : c->scalar, q);
+      return bk.compare_count((int)op, (int)dt, (int)mode, a, b, sc, n, c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
     });
     return fetch(c, rc, out);
   }
   int mask_logical(uint32_t op, const void* a, const void* b, void* y, int64_t n, void* s) override {
-    if (!bk.mask_logical) return broker::kBadArgument;
     return timed(s, pick(s, short_bytes(n, 1, 3)),
                  [&](hipStream_t q) { return bk.mask_logical((int)op, a, b, y, n, q); });
   }
   int where(uint32_t dt, const void* m, uint32_t flags, const void* a, const void* b, double sa, double sb, void* y,
             int64_t n, void* s) override {
-    if (!bk.where) return broker::kBadArgument;
     return timed(s, pick(s, short_bytes(n, elem_bytes(dt) * 3 + 1)),
                  [&](hipStream_t q) { return bk.where((int)dt, m, (int)flags, a, b, sa, sb, y, n, q); });
   }
   int compress(uint32_t dt, const void* x, const void* m, int64_t n, void* y, int64_t cap, void* s) override {
-    Ctx* c = (Ctx*)s;
-    if (!bk.compress) return broker::kBadArgument;
-    if (!c->compress_ws) {
-      if (bk.malloc_(&c->compress_ws, bk.compress_ws()) != 0) return broker::kOutOfMemory;
-      bk.compress_ws_init(c->compress_ws, c->s);
-    }
+    void* ws = workspace((Ctx*)s, BK_WS_COMPRESS);
+    if (!ws) return broker::kOutOfMemory;
     const int64_t es = dt == broker::kDtBool ? 1 : elem_bytes(dt);
     return timed(s, pick(s, short_bytes(n, 2 * es + 2)),
-                 [&](hipStream_t q) { return bk.compress((int)dt, x, m, n, y, cap, c->compress_ws, q); });
+                 [&](hipStream_t q) { return bk.compress((int)dt, x, m, n, y, cap, ws, q); });
   }
   // order statistics and histograms: results, edges and counts pass through
   // the session's device scratch (select results at 0, edges, then counts)
   static constexpr int64_t kStatsEdgesAt = 512;
   static constexpr int64_t kStatsCountsAt = kStatsEdgesAt + ((int64_t)broker::kMaxBins + 1) * 8;
   static constexpr int64_t kStatsBytes = kStatsCountsAt + (int64_t)broker::kMaxBins * 8;
-  bool stats_scratch(Ctx* c) { return c->stats || bk.malloc_((void**)&c->stats, kStatsBytes) == 0; }
+  bool stats_scratch(Ctx* c) { return c->stats || bk.malloc((void**)&c->stats, kStatsBytes) == 0; }
   int select(uint32_t dt, const void* x, int64_t n, const int64_t* ranks, uint32_t nranks, double* out,
              void* s) override {
     Ctx* c = (Ctx*)s;
-    if (!bk.select) return broker::kBadArgument;
     if (!stats_scratch(c)) return broker::kOutOfMemory;
-    if (!c->select_ws) {
-      if (bk.malloc_(&c->select_ws, bk.select_ws()) != 0) return broker::kOutOfMemory;
-      bk.select_ws_init(c->select_ws, c->s);
-    }
+    void* ws = workspace(c, BK_WS_SELECT);
+    if (!ws) return broker::kOutOfMemory;
     // one read of x per byte of the dtype
     const int rc = timed(s, pick(s, short_bytes(n, elem_bytes(dt), (int)elem_bytes(dt))), [&](hipStream_t q) {
-      return bk.select((int)dt, x, n, ranks, (int)nranks, c->stats, c->select_ws, q);
+      return bk.select((int)dt, x, n, ranks, (int)nranks, c->stats, ws, q);
     });
     if (rc != 0) return rc;
     if (hipMemcpyAsync(out, c->stats, ((size_t)nranks + 1) * 8, hipMemcpyDeviceToHost, c->s) != hipSuccess || !wait(c))
@@ -677,18 +601,15 @@ class HipDevice final : public broker::Device {
   int histogram(uint32_t dt, const void* x, int64_t n, const double* edges, uint32_t bins, uint64_t* counts,
                 void* s) override {
     Ctx* c = (Ctx*)s;
-    if (!bk.histogram) return broker::kBadArgument;
     if (!stats_scratch(c)) return broker::kOutOfMemory;
-    if (!c->hist_ws) {
-      if (bk.malloc_(&c->hist_ws, bk.hist_ws()) != 0) return broker::kOutOfMemory;
-      bk.hist_ws_init(c->hist_ws, c->s);
-    }
+    void* ws = workspace(c, BK_WS_HISTOGRAM);
+    if (!ws) return broker::kOutOfMemory;
     hipStream_t q0 = pick(s, short_bytes(n, elem_bytes(dt)));
     // (the caller's edges stay put until the wait below, or the one on the failure path)
     if (hipMemcpyAsync(c->stats + kStatsEdgesAt, edges, ((size_t)bins + 1) * 8, hipMemcpyHostToDevice, q0) != hipSuccess)
       return broker::kLaunchFailed;
     const int rc = timed(s, q0, [&](hipStream_t q) {
-      return bk.histogram((int)dt, x, n, c->stats + kStatsEdgesAt, (int)bins, c->stats + kStatsCountsAt, c->hist_ws, q);
+      return bk.histogram((int)dt, x, n, c->stats + kStatsEdgesAt, (int)bins, c->stats + kStatsCountsAt, ws, q);
     });
     if (rc != 0) {
       hipStreamSynchronize(q0);
@@ -699,7 +620,7 @@ class HipDevice final : public broker::Device {
       return broker::kLaunchFailed;
     return 0;
   }
-  const char* last_error() override { return bk.last_error ? bk.last_error() : ""; }
+  const char* last_error() override { return bk.last_error(); }
   void info(int64_t v[5]) override {
     size_t fr = 0, tot = 0;
     hipMemGetInfo(&fr, &tot);

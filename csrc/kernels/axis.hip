@@ -175,10 +175,10 @@ enum StatOp : int { kStatMax = 0, kStatMin, kStatVar, kStatStd, kStatCount };
 enum Mode : int { kMax = 0, kMin, kSum, kSqDev };
 
 // partials (chunks x columns), the column means between the two launches of a
-// column variance, one ticket per column block -- the sizes of reduce.hip's
-// axis workspace (kAxisWsDoubles, kAxisTickets), which set the width limit
-constexpr int64_t kWsDoubles = 1 << 18;
-constexpr int64_t kTickets = 4096;
+// column variance, one ticket per column block -- in the sizes of reduce.hip's
+// axis workspace (bk_ticket.hpp)
+constexpr int64_t kWsDoubles = kAxisWsDoubles;
+constexpr int64_t kTickets = kAxisTickets;
 constexpr int kColWaves = 16;
 
 template <typename T> struct alignas(16) V16 { T v[16 / sizeof(T)]; };
@@ -454,15 +454,19 @@ int launch_stat(int op, const T* x, int64_t rows, int64_t cols, int64_t ld, int 
 }
 
 }  // namespace axis
+
+// partials and column means, then the tickets
+WsLayout axis_stat_ws_layout() {
+  const int64_t doubles = 2 * axis::kWsDoubles * (int64_t)sizeof(double);
+  const int64_t tickets = axis::kTickets * (int64_t)sizeof(unsigned);
+  return {doubles + tickets, doubles, tickets};
+}
+
 }  // namespace bk
 
 using namespace bk;
 
-// y[rows x cols] (row stride ldy) = a[rows x cols] (row stride lda) OP v, with
-// v[cols] along the rows (kind 0) or v[rows] down the columns (kind 1);
-// swapped: v OP a.  op: the codes of bk_binary.  f32 / f64.  y may be a
-// itself (same pointer and stride); any other overlap of y with a or v is
-// refused.
+// (contracts of the entry points: beekern.h)
 BK_API int bk_broadcast(int op, int dtype, int kind, int swapped, const void* a, int64_t rows, int64_t cols, int64_t lda,
                         const void* v, void* y, int64_t ldy, hipStream_t stream) {
   if (!a || !v || !y || rows < 0 || cols < 0 || lda < cols || ldy < cols || op < 0 || op >= kBinCount ||
@@ -483,23 +487,6 @@ BK_API int bk_broadcast(int op, int dtype, int kind, int swapped, const void* a,
   return axis::dispatch_broadcast<float>(op, kind, swapped != 0, a, v, y, rows, cols, lda, ldy, stream, Ops{});
 }
 
-BK_API int64_t bk_axis_stat_workspace_bytes() {
-  return 2 * axis::kWsDoubles * (int64_t)sizeof(double) + axis::kTickets * (int64_t)sizeof(unsigned);
-}
-
-// A fresh workspace's tickets must read zero (each launch re-arms its own).
-BK_API int bk_axis_stat_workspace_init(void* ws, hipStream_t stream) {
-  if (!ws) return kBadArgument;
-  if (hipMemsetAsync((char*)ws + 2 * axis::kWsDoubles * sizeof(double), 0, axis::kTickets * sizeof(unsigned), stream) !=
-      hipSuccess)
-    return kLaunchFailed;
-  return kOk;
-}
-
-// out[cols] (axis 0) or out[rows] (axis 1) = max (op 0), min (1), variance (2)
-// or standard deviation (3) of x[rows x cols] (row stride ld), in x's dtype
-// (f32 / f64; f64 arithmetic throughout).  divisor: n - ddof of the variance
-// (finite, > 0; unused by max / min).  ws: the axis-stat workspace.
 BK_API int bk_axis_stat(int op, int dtype, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis,
                         double divisor, void* out, void* ws, hipStream_t stream) {
   if (!x || !out || !ws || rows <= 0 || cols <= 0 || ld < cols || (axis != 0 && axis != 1) || op < 0 ||

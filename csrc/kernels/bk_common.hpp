@@ -15,7 +15,7 @@
 #include <utility>
 #include <type_traits>
 
-#define BK_API extern "C" __attribute__((visibility("default")))
+#include "beekern.h"  // BK_API, the limits and one declaration of every entry point
 
 namespace bk {
 
@@ -70,6 +70,19 @@ inline unsigned stream_grid(int64_t work_items, int block, int max_blocks_per_cu
 }
 
 inline int launch_status() { return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed; }
+
+// A ticketed workspace (enum BkWorkspace): its size and the region a fresh one
+// must have zeroed.  Each kind's numbers sit next to the layout they describe;
+// bk_workspace_bytes / bk_workspace_init (runtime.cpp) are their only readers.
+struct WsLayout {
+  int64_t bytes, zero_at, zero_bytes;
+};
+WsLayout reduce_ws_layout();       // reduce.hip
+WsLayout reduce_axis_ws_layout();  // reduce.hip
+WsLayout axis_stat_ws_layout();    // axis.hip
+WsLayout compress_ws_layout();     // mask.hip
+WsLayout select_ws_layout();       // stats.hip
+WsLayout histogram_ws_layout();    // stats.hip
 
 // Streaming 16-B accesses.  NT = non-temporal (nt cache policy): measured on
 // MI355X for 1e8 f64 (tools/probe/reduce_probe.hip) a square-copy went

@@ -3,7 +3,7 @@
 //
 // Every block publishes its partial, then takes a ticket; the block holding
 // the last ticket folds the partials and re-arms the ticket for the next
-// launch on this workspace.  Tickets start at zero (bk_reduce_workspace_init).
+// launch on this workspace.  Tickets start at zero (bk_workspace_init).
 // No block ever waits for another: the last one to arrive does the fold.
 //
 // Blocks sit on different XCDs, each with its own L2.  Partials are written
@@ -28,8 +28,13 @@ namespace bk {
 
 constexpr int kRedBlock = 256;
 // the reduction workspace holds kRedMaxBlocks f64 partials, then the ticket
-// (its own 256 B): bk_reduce_workspace_bytes
+// (its own 256 B): BK_WS_REDUCE
 constexpr int kRedMaxBlocks = 32768;
+// the axis workspaces of reduce.hip and axis.hip: chunks x columns f64 partials
+// (which set the width limit of a column reduction), then one ticket per
+// column block (<= 2048 at 262144 columns)
+constexpr int64_t kAxisWsDoubles = BK_MAX_AXIS0_COLUMNS;
+constexpr int64_t kAxisTickets = 4096;
 
 template <typename T>
 __device__ __forceinline__ void publish(T* p, T v) {

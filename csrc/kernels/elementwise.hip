@@ -234,6 +234,7 @@ int dispatch_binary(int op, int mode, const void* a, const void* b, double sc, v
 
 using namespace bk;
 
+// (contracts of the entry points: beekern.h)
 BK_API int bk_unary(int op, int dtype, const void* x, void* y, int64_t n, hipStream_t stream) {
   if (!x || !y || n < 0 || op < 0 || op >= kUnaryCount) return kBadArgument;
   if (n == 0) return kOk;
@@ -246,7 +247,6 @@ BK_API int bk_unary(int op, int dtype, const void* x, void* y, int64_t n, hipStr
   return kBadArgument;
 }
 
-// mode: 0 = array (op) array, 1 = array (op) scalar, 2 = scalar (op) array
 BK_API int bk_binary(int op, int dtype, int mode, const void* a, const void* b, double scalar, void* y, int64_t n,
                      hipStream_t stream) {
   if (!a || !y || n < 0 || op < 0 || op >= kBinCount || mode < 0 || mode > 2 || (mode == 0 && !b))

@@ -589,6 +589,7 @@ using namespace bk;
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// (contracts of the entry points: beekern.h)
 BK_API int bk_gemm_bf16_fast_ok(int M, int N, int K, int lda, int ldb) {
   return M > 0 && N > 0 && K > 0 && M % BM == 0 && N % BN == 0 && K % BK == 0 && lda % 8 == 0 && ldb % 8 == 0;
 }
@@ -613,9 +614,7 @@ static bool edge_ok(int M, int N, int K, int lda, int ldb) {
 // dimensions are multiples of 8; only the rest reach the generic kernel.
 // Large non-tile-multiple shapes take the 4-wave 256x256 kernel in its edge
 // mode (variant 7; K % 8 == 0) when they fill the chip.
-// variant: 0 = auto, 1 = generic, 2 = 128x128, 3 = 256x256 (4-wave or 8-wave
-// by K), 4 = 256x256 8-wave, 5 = 256x256 4-wave, 6 = 128x128 edge, 7 = 256x256
-// 4-wave edge, 8 = skinny (N <= 16: a matrix-vector product) (benchmarks, tests).
+// (the variant numbers: bk_gemm_bf16_tn_variant in beekern.h)
 static int auto_variant(bool ok256, bool ok128, bool okedge, bool ok256e, bool okskinny, int M, int N) {
   if (okskinny) return 8;  // GEMV-shaped (N <= 16): read A once, no mostly-empty tiles
   const int64_t tiles256 = (int64_t)((M + 255) / 256) * ((N + 255) / 256);
@@ -711,7 +710,6 @@ BK_API int bk_gemm_bf16_tn_variant(const void* A, const void* Bt, void* C, int M
   return launch_status();
 }
 
-// Which kernel `variant 0` resolves to for these operands (diagnostics).
 BK_API int bk_gemm_bf16_pick(const void* A, const void* Bt, const void* C, int M, int N, int K, int lda, int ldb,
                              int ldc, int out_dtype) {
   const bool al = aligned16(A) && aligned16(Bt);
@@ -721,11 +719,6 @@ BK_API int bk_gemm_bf16_pick(const void* A, const void* Bt, const void* C, int M
                       skinny_ok(A, Bt, N, K, lda, ldb), M, N);
 }
 
-// C = alpha * A . B + beta * C with B stored [K][N] (leading dimension ldb):
-// the 4-wave 256x256 kernel reading B through transposed LDS reads, no
-// transpose pass.  Tile-multiple shapes (M, N % 256, K % 64) with 16-B
-// aligned operands only: kBadArgument otherwise (callers transpose B and use
-// bk_gemm_bf16_tn).
 BK_API int bk_gemm_bf16_nn_ok(const void* A, const void* B, const void* C, int M, int N, int K, int lda, int ldb,
                               int ldc, int out_dtype) {
   return A && B && C && (out_dtype == kBF16 || out_dtype == kF32) && lda >= K && ldc >= N && aligned16(A) &&
@@ -739,7 +732,6 @@ BK_API int bk_gemm_bf16_nn(const void* A, const void* B, void* C, int M, int N, 
   return launch_status();
 }
 
-// C = alpha * A . Bt^T + beta * C.  out_dtype: kBF16 or kF32.
 BK_API int bk_gemm_bf16_tn(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc,
                            float alpha, float beta, int out_dtype, hipStream_t stream) {
   return bk_gemm_bf16_tn_variant(A, Bt, C, M, N, K, lda, ldb, ldc, alpha, beta, out_dtype, 0, stream);
@@ -758,9 +750,6 @@ BK_API int bk_transpose_bf16(const void* in, void* out, int rows, int cols, int 
   return launch_status();
 }
 
-// out[cols x rows] (bf16) = transpose of in[rows x cols] (src_dtype kBF16,
-// kF32 or kF64).  Wide inputs need the 8-aligned, 16-B aligned shape of the
-// vector kernel (kBadArgument otherwise: the caller casts, then transposes).
 BK_API int bk_transpose_to_bf16(int src_dtype, const void* in, void* out, int rows, int cols, int ld_in, int ld_out,
                                 hipStream_t stream) {
   if (src_dtype == kBF16) return bk_transpose_bf16(in, out, rows, cols, ld_in, ld_out, stream);
@@ -775,9 +764,6 @@ BK_API int bk_transpose_to_bf16(int src_dtype, const void* in, void* out, int ro
   return launch_status();
 }
 
-// out[cols x rows] = transpose of in[rows x cols].  dst_dtype kBF16 converts
-// (bk_transpose_to_bf16); dst_dtype == src_dtype moves the bits (2-, 4- or
-// 8-byte elements).
 BK_API int bk_transpose(int src_dtype, int dst_dtype, const void* in, void* out, int rows, int cols, int ld_in,
                         int ld_out, hipStream_t stream) {
   if (dst_dtype == kBF16) return bk_transpose_to_bf16(src_dtype, in, out, rows, cols, ld_in, ld_out, stream);

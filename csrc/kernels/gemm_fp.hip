@@ -820,10 +820,7 @@ __global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ s
 
 using namespace bk;
 
-// C[M][N] = op(A) . op(B) in f64 (dtype kF64) or f32 (kF32), row-major C with
-// leading dimension ldc.  trans_a: A is given as its transpose, a [K][M]
-// buffer (lda >= M); else [M][K] (lda >= K).  trans_b: B given as a [N][K]
-// buffer (ldb >= K); else [K][N] (ldb >= N).  Never reads C.
+// (contracts of the entry points: beekern.h)
 BK_API int bk_gemm_fp(int dtype, int trans_a, int trans_b, const void* A, const void* B, void* C, int M, int N, int K,
                       int64_t lda, int64_t ldb, int64_t ldc, hipStream_t stream) {
   if (dtype != kF64 && dtype != kF32) return kBadArgument;
@@ -842,15 +839,7 @@ BK_API int bk_gemm_fp(int dtype, int trans_a, int trans_b, const void* A, const 
 }
 
 
-// ---- C = op(A) . op(B) for f32 operands on the bf16 MFMA GEMM, f32-level
-// error (the six-piece split above).  Same operand conventions as
-// bk_gemm_fp.  `ws` (16-B aligned, bk_gemm_f32x6_workspace_bytes) holds a
-// flag word and the split operands A' [M][6 Kp], B' [N][6 Kp].  Operands the
-// split cannot represent (inf / NaN, |x| >= 2^127, 0 < |x| < 2^-100) make the
-// plain f32 kernel recompute C, gated on the flag (no host sync).
-BK_API int bk_gemm_bf16_tn(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc,
-                           float alpha, float beta, int out_dtype, hipStream_t stream);
-
+// ---- bk_gemm_f32x6: f32 operands on the bf16 MFMA GEMM (the six-piece split above)
 static int64_t f32x6_kp(int K) { return ((int64_t)K + fp::kSplitTile - 1) / fp::kSplitTile * fp::kSplitTile; }
 
 BK_API int64_t bk_gemm_f32x6_workspace_bytes(int M, int N, int K) {

@@ -601,12 +601,15 @@ int reduce_bool(int op, const void* a, int64_t n, void* workspace, void* out, hi
   return launch_count<uint32_t, 0, kCountMask>(a, nullptr, 0.0, n, final_op, (double*)workspace, (double*)out, stream);
 }
 
+// counts and offsets, then the ticket's 256 B
+WsLayout compress_ws_layout() { return {mask::kCzWsBytes, 2ll * mask::kCzMaxBlocks * 8, 256}; }
+
 }  // namespace bk
 
 using namespace bk;
 using namespace bk::mask;
 
-// mode: 0 = array (op) array, 1 = array (op) scalar; mask_out: n bytes of 0 / 1
+// (contracts of the entry points: beekern.h)
 BK_API int bk_compare(int op, int dtype, int mode, const void* a, const void* b, double scalar, void* mask_out,
                       int64_t n, hipStream_t stream) {
   if (!a || !mask_out || n < 0 || op < 0 || op >= kCmpCount || mode < 0 || mode > 1 || (mode == 0 && !b))
@@ -621,8 +624,6 @@ BK_API int bk_compare(int op, int dtype, int mode, const void* a, const void* b,
   }
 }
 
-// the number of true comparisons as ONE double in *out, no mask written.
-// workspace: bk_reduce_workspace_bytes() bytes (the reductions' own).
 BK_API int bk_compare_count(int op, int dtype, int mode, const void* a, const void* b, double scalar, int64_t n,
                             void* workspace, void* out, hipStream_t stream) {
   if (!a || !workspace || !out || n < 0 || op < 0 || op >= kCmpCount || mode < 0 || mode > 1 || (mode == 0 && !b))
@@ -638,7 +639,6 @@ BK_API int bk_compare_count(int op, int dtype, int mode, const void* a, const vo
   return kBadArgument;
 }
 
-// op: 0 and, 1 or, 2 xor, 3 not (b unused); inputs normalised with != 0
 BK_API int bk_mask_logical(int op, const void* a, const void* b, void* out, int64_t n, hipStream_t stream) {
   if (!a || !out || n < 0 || op < 0 || op >= kLogicalCount || (op != kNot && !b)) return kBadArgument;
   if (n == 0) return kOk;
@@ -650,9 +650,6 @@ BK_API int bk_mask_logical(int op, const void* a, const void* b, void* out, int6
   }
 }
 
-// out[i] = mask[i] ? A : B; flags bit 0: A is the scalar sa, bit 1: B is the
-// scalar sb.  Scalars are converted to the dtype once (f32: RNE; bf16: f32
-// then RNE); array values move as bits.
 BK_API int bk_where(int dtype, const void* mask, int flags, const void* a, const void* b, double sa, double sb,
                     void* out, int64_t n, hipStream_t stream) {
   if (!mask || !out || n < 0 || (flags & ~3) != 0 || (!(flags & 1) && !a) || (!(flags & 2) && !b)) return kBadArgument;
@@ -674,17 +671,6 @@ BK_API int bk_where(int dtype, const void* mask, int flags, const void* a, const
   return launch_where<uint16_t>(mask, flags, a, b, host_bf16_bits(fa), host_bf16_bits(fb), out, n, stream);
 }
 
-BK_API int64_t bk_compress_workspace_bytes() { return kCzWsBytes; }
-
-// A fresh workspace's ticket must read zero (each launch re-arms its own).
-BK_API int bk_compress_workspace_init(void* ws, hipStream_t stream) {
-  if (!ws) return kBadArgument;
-  if (hipMemsetAsync((char*)ws + 2ll * kCzMaxBlocks * 8, 0, 256, stream) != hipSuccess) return kLaunchFailed;
-  return kOk;
-}
-
-// out[0 : min(count, cap)] = x[mask] in index order (two launches); dtype:
-// f32 / f64 / bf16 / bool, moved by size.  A write at index >= cap is dropped.
 BK_API int bk_compress(int dtype, const void* x, const void* mask, int64_t n, void* out, int64_t cap, void* workspace,
                        hipStream_t stream) {
   if (!x || !mask || !out || !workspace || n < 0 || cap < 0) return kBadArgument;

@@ -139,8 +139,7 @@ __global__ __launch_bounds__(256) void philox_normal_f64(double* __restrict__ ou
 
 using namespace bk;
 
-// dtype: kF64, kF32 or kBF16 (the f32 stream, rounded).  `offset` advances the counter so successive draws from
-// one seed never overlap (the Python side keeps the running offset).
+// (contracts of the entry points: beekern.h)
 BK_API int bk_rand_uniform(void* out, int64_t n, int dtype, uint64_t seed, uint64_t offset, double lo, double hi,
                            hipStream_t stream) {
   if (!out || n < 0) return kBadArgument;

@@ -484,8 +484,7 @@ int dispatch_reduce(int op, const void* a, const void* b, int64_t n, double* ws,
 // workspace and the last chunk block of each column block (completion
 // tickets, as above) folds them in chunk order (deterministic) -- one launch.
 // axis 1 (per row): one wave per row, lanes stride the row, DPP wave sum.
-constexpr int64_t kAxisWsDoubles = 1 << 18;  // 2 MiB: chunks x columns partials
-constexpr int64_t kAxisTickets = 4096;       // one per column block (<= 2048 at 262144 columns)
+// (kAxisWsDoubles -- 2 MiB of chunks x columns partials -- and kAxisTickets: bk_ticket.hpp)
 
 // out[col] = scale * the chunk partials of `col` folded in a fixed order: four
 // chains (chunks c, c+4, c+8, c+12) so a thread's loads are in flight together
@@ -681,12 +680,23 @@ int launch_axis(const T* x, int64_t rows, int64_t cols, int64_t ld, int axis, TO
   return launch_status();
 }
 
+// partials, then the completion ticket (its own 256 B)
+WsLayout reduce_ws_layout() {
+  const int64_t partials = kRedMaxBlocks * (int64_t)sizeof(double);
+  return {partials + 256, partials, 256};
+}
+// partials, then the tickets
+WsLayout reduce_axis_ws_layout() {
+  const int64_t partials = kAxisWsDoubles * (int64_t)sizeof(double);
+  const int64_t tickets = kAxisTickets * (int64_t)sizeof(unsigned);
+  return {partials + tickets, partials, tickets};
+}
+
 }  // namespace bk
 
 using namespace bk;
 
-// sum (op 0) or square-sum (op 1) of the uniform [lo, hi) draw of n values
-// at (seed, offset) -- without materialising it.  dtype kF64 or kF32.
+// (contracts of the entry points: beekern.h)
 BK_API int bk_rand_reduce(int op, int dtype, int64_t n, uint64_t seed, uint64_t offset, double lo, double hi,
                           void* workspace, void* out, hipStream_t stream) {
   if (!workspace || !out || n < 0 || (op != kRedSum && op != kRedSquareSum) || (dtype != kF64 && dtype != kF32))
@@ -716,19 +726,6 @@ BK_API int bk_rand_reduce(int op, int dtype, int64_t n, uint64_t seed, uint64_t 
   return launch_status();
 }
 
-// partials, then the completion ticket (its own 256 B)
-BK_API int bk_reduce_workspace_bytes() { return kRedMaxBlocks * (int)sizeof(double) + 256; }
-
-// A fresh workspace's tickets must read zero (each launch re-arms its own).
-BK_API int bk_reduce_workspace_init(void* workspace, hipStream_t stream) {
-  if (!workspace) return kBadArgument;
-  if (hipMemsetAsync((char*)workspace + kRedMaxBlocks * sizeof(double), 0, 256, stream) != hipSuccess)
-    return kLaunchFailed;
-  return kOk;
-}
-
-// out: ONE double on the device.  workspace: bk_reduce_workspace_bytes() bytes.
-// b is only read for kRedDot and kRedMaxAbsDiff (same length and dtype as a).
 BK_API int bk_reduce(int op, int dtype, const void* a, const void* b, int64_t n, void* workspace, void* out,
                      hipStream_t stream) {
   if (!a || !out || !workspace || n < 0 || op < 0 || op >= kRedCount || ((op == kRedDot || op == kRedMaxAbsDiff) && !b)) return kBadArgument;
@@ -742,21 +739,6 @@ BK_API int bk_reduce(int op, int dtype, const void* a, const void* b, int64_t n,
   return kBadArgument;
 }
 
-BK_API int64_t bk_reduce_axis_workspace_bytes() {
-  return kAxisWsDoubles * (int64_t)sizeof(double) + kAxisTickets * (int64_t)sizeof(unsigned);
-}
-
-BK_API int bk_reduce_axis_workspace_init(void* ws, hipStream_t stream) {
-  if (!ws) return kBadArgument;
-  if (hipMemsetAsync((char*)ws + kAxisWsDoubles * sizeof(double), 0, kAxisTickets * sizeof(unsigned), stream) !=
-      hipSuccess)
-    return kLaunchFailed;
-  return kOk;
-}
-
-// out[cols] (axis 0) or out[rows] (axis 1) = sum (op 0) or mean (op 1) of
-// x[rows x cols] (row stride ld).  out dtype: f64 for f64 input, f32 for f32
-// and bf16 input (f64 accumulation throughout).  ws: the axis workspace.
 BK_API int bk_reduce_axis(int op, int dtype, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis, void* out,
                           void* ws, hipStream_t stream) {
   if (!x || !out || !ws || rows <= 0 || cols <= 0 || ld < cols || (axis != 0 && axis != 1) || (op != 0 && op != 1))

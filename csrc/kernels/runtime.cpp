@@ -32,11 +32,11 @@
 #include <unordered_map>
 #include <vector>
 
-#define BK_API extern "C" __attribute__((visibility("default")))
+#include "bk_common.hpp"
+
+using namespace bk;
 
 namespace {
-
-enum Status : int { kOk = 0, kBadArgument = 1, kLaunchFailed = 2, kOutOfMemory = 3, kQuotaExceeded = 4, kNotInitialized = 5 };
 
 std::mutex g_mu;
 int g_device = -1;
@@ -184,16 +184,38 @@ bool seg_grow(size_t need) {
   return true;
 }
 
+// the layout of a workspace kind (enum BkWorkspace); false for an unknown kind
+bool ws_layout(int kind, WsLayout* out) {
+  switch (kind) {
+    case BK_WS_REDUCE: *out = reduce_ws_layout(); return true;
+    case BK_WS_REDUCE_AXIS: *out = reduce_axis_ws_layout(); return true;
+    case BK_WS_AXIS_STAT: *out = axis_stat_ws_layout(); return true;
+    case BK_WS_COMPRESS: *out = compress_ws_layout(); return true;
+    case BK_WS_SELECT: *out = select_ws_layout(); return true;
+    case BK_WS_HISTOGRAM: *out = histogram_ws_layout(); return true;
+  }
+  return false;
+}
+
 }  // namespace
 
+// (contracts of the entry points: beekern.h)
 BK_API const char* bk_last_error() { return g_err; }
 
 BK_API int bk_version() { return 10000; }  // 1.0.0
 
-// Select the device, create the context and load this code object so the
-// first user kernel launch pays nothing (measured: ~60-480 ms hipInit and
-// ~90-140 ms first-launch module load on MI355X, paid while the sandbox
-// waits in the warm pool instead of on the request path).
+BK_API int64_t bk_workspace_bytes(int kind) {
+  WsLayout l;
+  return ws_layout(kind, &l) ? l.bytes : 0;
+}
+
+BK_API int bk_workspace_init(int kind, void* ws, hipStream_t stream) {
+  WsLayout l;
+  if (!ws || !ws_layout(kind, &l)) return kBadArgument;
+  if (hipMemsetAsync((char*)ws + l.zero_at, 0, (size_t)l.zero_bytes, stream) != hipSuccess) return kLaunchFailed;
+  return kOk;
+}
+
 BK_API int bk_init(int device) {
   std::lock_guard<std::mutex> lk(g_mu);
   hipError_t e = hipSetDevice(device);
@@ -321,9 +343,6 @@ BK_API int bk_empty_cache() {
   return release_cache_locked();
 }
 
-// Serve large blocks from segments from now on, and reserve one of `bytes`
-// now (the kernel broker at start-up): the first requests' large
-// allocations are carved from it.
 BK_API int bk_reserve(int64_t bytes) {
   {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -337,7 +356,6 @@ BK_API int bk_reserve(int64_t bytes) {
   return kOk;
 }
 
-// stats[0]=in_use, [1]=cached (small-block cache + free segment bytes), [2]=peak, [3]=quota
 BK_API int bk_memory_stats(int64_t* stats) {
   if (!stats) return kBadArgument;
   std::lock_guard<std::mutex> lk(g_mu);
@@ -351,7 +369,6 @@ BK_API int bk_memory_stats(int64_t* stats) {
 }
 
 BK_API int bk_memcpy(void* dst, const void* src, int64_t nbytes, int kind, hipStream_t stream) {
-  // kind: 1 = H2D, 2 = D2H, 3 = D2D (hipMemcpyKind values); synchronous on `stream`
   if (nbytes == 0) return kOk;
   if (!dst || !src || nbytes < 0) return kBadArgument;
   hipError_t e = hipMemcpyAsync(dst, src, (size_t)nbytes, (hipMemcpyKind)kind, stream);
@@ -374,30 +391,13 @@ BK_API int bk_sync(hipStream_t stream) {
   return kOk;
 }
 
-// entry points of the kernel translation units (same library)
-BK_API int bk_rand_uniform(void*, int64_t, int, uint64_t, uint64_t, double, double, hipStream_t);
-BK_API int bk_unary(int, int, const void*, void*, int64_t, hipStream_t);
-BK_API int bk_reduce(int, int, const void*, const void*, int64_t, void*, void*, hipStream_t);
-BK_API int bk_rand_reduce(int, int, int64_t, uint64_t, uint64_t, double, double, void*, void*, hipStream_t);
-BK_API int bk_reduce_workspace_bytes();
-BK_API int bk_reduce_workspace_init(void*, hipStream_t);
-BK_API int bk_gemm_bf16_tn_variant(const void*, const void*, void*, int, int, int, int, int, int, float, float, int, int,
-                                   hipStream_t);
-BK_API int bk_transpose_bf16(const void*, void*, int, int, int, int, hipStream_t);
-
-// Run one tiny launch from every kernel module so HIP loads the code objects
-// now: with deferred loading the first launch from each module costs tens of
-// ms (measured in the served path: the first bk.rand 128 ms, the first
-// rand_reduce 34 ms; profiles/archive/r1_served_path_final_ranges.csv), which a
-// long-lived process (the kernel broker) should pay at startup, not on a
-// request.  Returns the first failure.
 BK_API int bk_preload(hipStream_t stream) {
   void *buf = nullptr, *ws = nullptr, *scalar = nullptr;
   constexpr int64_t kDim = 256;
   const int64_t bytes = 3 * kDim * kDim * 4;  // A, B (bf16) + C (f32) of a 256^3 GEMM
   int rc = bk_malloc(&buf, bytes);
-  if (rc == kOk) rc = bk_malloc(&ws, bk_reduce_workspace_bytes());
-  if (rc == kOk) rc = bk_reduce_workspace_init(ws, stream);
+  if (rc == kOk) rc = bk_malloc(&ws, bk_workspace_bytes(BK_WS_REDUCE));
+  if (rc == kOk) rc = bk_workspace_init(BK_WS_REDUCE, ws, stream);
   if (rc == kOk) rc = bk_malloc(&scalar, 256);
   if (rc == kOk) {
     char* a = (char*)buf;
@@ -425,7 +425,6 @@ BK_API int bk_preload(hipStream_t stream) {
   return rc;
 }
 
-// info[0]=CUs, [1]=total bytes, [2]=free bytes, [3]=clock kHz, [4]=LDS/CU bytes
 BK_API int bk_device_info(int64_t* info, char* name, int name_len) {
   if (!info) return kBadArgument;
   int dev = 0;
@@ -446,7 +445,6 @@ BK_API int bk_device_info(int64_t* info, char* name, int name_len) {
   return kOk;
 }
 
-// Timing helper for benches: elapsed ms between two events recorded on stream.
 BK_API int bk_event_pair_create(void** start, void** stop) {
   if (hipEventCreate((hipEvent_t*)start) != hipSuccess) return kLaunchFailed;
   if (hipEventCreate((hipEvent_t*)stop) != hipSuccess) return kLaunchFailed;

@@ -27,11 +27,11 @@ constexpr int kUnroll = 4;          // 16-B loads in flight per lane
 constexpr int kMaxBlocks = 1024;    // 4 per CU; every block merges its counts into the table once
 constexpr int kPeel = 2;            // wave-combined indices before the per-lane atomics
 
-constexpr int kMaxRanks = 32;
+constexpr int kMaxRanks = BK_MAX_RANKS;
 constexpr int kDigitBits = 8;
 constexpr int kDigits = 1 << kDigitBits;
 
-constexpr int kMaxBins = 4096;
+constexpr int kMaxBins = BK_MAX_BINS;
 
 template <typename T> struct alignas(16) V16 {
   static constexpr int N = 16 / sizeof(T);
@@ -400,24 +400,17 @@ int launch_histogram(const void* x, int64_t n, const double* edges, int bins, un
 }
 
 }  // namespace stats
+
+// A fresh workspace reads zero everywhere (table, NaN count, ticket); every call leaves it so.
+WsLayout select_ws_layout() { return {(int64_t)sizeof(stats::SelectWs), 0, (int64_t)sizeof(stats::SelectWs)}; }
+WsLayout histogram_ws_layout() { return {(int64_t)sizeof(stats::HistWs), 0, (int64_t)sizeof(stats::HistWs)}; }
+
 }  // namespace bk
 
 using namespace bk;
 using namespace bk::stats;
 
-BK_API int64_t bk_select_workspace_bytes() { return (int64_t)sizeof(SelectWs); }
-
-// A fresh workspace reads zero everywhere (table, NaN count, ticket); every call leaves it so.
-BK_API int bk_select_workspace_init(void* ws, hipStream_t stream) {
-  if (!ws) return kBadArgument;
-  return hipMemsetAsync(ws, 0, sizeof(SelectWs), stream) == hipSuccess ? kOk : kLaunchFailed;
-}
-
-// out[i] = np.sort(x)[ranks[i]] widened to f64 for the nranks (1..32) 0-based
-// ranks, each in [0, n); out[nranks] = the number of NaNs in x (they sort
-// last).  `ranks` is read on the host during the call; x, out and the
-// workspace (bk_select_workspace_bytes, initialised once) are device memory.
-// One launch per byte of the dtype; x is only read.
+// (contracts of the entry points: beekern.h)
 BK_API int bk_select(int dtype, const void* x, int64_t n, const int64_t* ranks, int nranks, void* out,
                      void* workspace, hipStream_t stream) {
   if (!x || !ranks || !out || !workspace || n <= 0 || nranks < 1 || nranks > kMaxRanks) return kBadArgument;
@@ -438,17 +431,7 @@ BK_API int bk_select(int dtype, const void* x, int64_t n, const int64_t* ranks, 
 }
 
 BK_API int bk_histogram_max_bins() { return kMaxBins; }
-BK_API int64_t bk_histogram_workspace_bytes() { return (int64_t)sizeof(HistWs); }
-BK_API int bk_histogram_workspace_init(void* ws, hipStream_t stream) {
-  if (!ws) return kBadArgument;
-  return hipMemsetAsync(ws, 0, sizeof(HistWs), stream) == hipSuccess ? kOk : kLaunchFailed;
-}
 
-// counts[i] (u64, i < bins) = the number of elements v of x, widened to f64,
-// with edges[i] <= v < edges[i + 1] (the last bin also takes v ==
-// edges[bins]): np.histogram's rule.  edges: bins + 1 non-decreasing f64 in
-// device memory, 1 <= bins <= 4096.  NaNs and values outside the edges count
-// nowhere; what counts held before does not matter.  One launch.
 BK_API int bk_histogram(int dtype, const void* x, int64_t n, const void* edges, int bins, void* counts,
                         void* workspace, hipStream_t stream) {
   if (!x || !edges || !counts || !workspace || n < 0 || bins < 1 || bins > kMaxBins) return kBadArgument;

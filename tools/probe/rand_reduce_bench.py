@@ -15,7 +15,8 @@ s = torch.cuda.current_stream().cuda_stream
 rr = lib.bk_rand_reduce
 rr.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
                ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-ws = torch.zeros(lib.bk_reduce_workspace_bytes() // 8 + 1, dtype=torch.float64, device="cuda")  # tickets start at 0
+ws = torch.empty(lib.bk_workspace_bytes(0), dtype=torch.uint8, device="cuda")  # 0: BK_WS_REDUCE
+assert lib.bk_workspace_init(0, ws.data_ptr(), s) == 0  # tickets start at 0
 out = torch.empty(1, dtype=torch.float64, device="cuda")
 
 
