@@ -106,8 +106,14 @@ BK_API int bk_rand_normal(void* out, int64_t n, int dtype, uint64_t seed, uint64
                           hipStream_t stream);
 
 // ---- elementwise (elementwise.hip) ------------------------------------------------------
+// f64 computes in f64; f32 and bf16 compute in f32 (bf16 rounds once on store).
+// abs clears the sign bit: abs(-0.0) = +0.0 and a NaN comes out positive, as numpy.absolute.
+// relu is numpy.maximum(x, 0): NaN in gives NaN out; both zeros and every negative give +0.0.
 BK_API int bk_unary(int op, int dtype, const void* x, void* y, int64_t n, hipStream_t stream);
-// mode: 0 = array (op) array, 1 = array (op) scalar, 2 = scalar (op) array
+// mode: 0 = array (op) array, 1 = array (op) scalar, 2 = scalar (op) array.
+// The scalar is converted once to the compute type (f64; f32 for f32 and bf16
+// arrays) and the arithmetic runs there: x + 0.1 on f32 adds float(0.1), as
+// numpy does for a Python scalar.
 BK_API int bk_binary(int op, int dtype, int mode, const void* a, const void* b, double scalar, void* y, int64_t n,
                      hipStream_t stream);
 BK_API int bk_cast(int src_dtype, int dst_dtype, const void* x, void* y, int64_t n, hipStream_t stream);

@@ -35,12 +35,14 @@ template <> struct Elem<uint16_t> {  // bf16 bits
 template <int OP, typename C>
 __device__ __forceinline__ C unary(C x) {
   if constexpr (OP == kUnarySquare) return x * x;
-  else if constexpr (OP == kUnaryAbs) return x < C(0) ? -x : x;
+  // numpy.absolute: the sign bit cleared, so abs(-0.0) = +0.0 and a NaN comes out positive
+  else if constexpr (OP == kUnaryAbs) return fabs(x);
   else if constexpr (OP == kUnaryNeg) return -x;
   else if constexpr (OP == kUnarySqrt) return sqrt(x);
   else if constexpr (OP == kUnaryExp) return exp(x);
   else if constexpr (OP == kUnaryLog) return log(x);
-  else if constexpr (OP == kUnaryRelu) return x > C(0) ? x : C(0);
+  // numpy.maximum(x, 0): NaN stays NaN (as kBinMax); zeros and negatives give +0.0
+  else if constexpr (OP == kUnaryRelu) return (x > C(0) || x != x) ? x : C(0);
   else if constexpr (OP == kUnarySin) return sin(x);
   else if constexpr (OP == kUnaryCos) return cos(x);
   else if constexpr (OP == kUnaryTanh) return tanh(x);

@@ -120,15 +120,22 @@ class HostDriver:
 
     def binary(self, op, dt, mode, a, b, sc, y, n) -> None:
         self.launches.append(("binary", op, n))
-        x = self._load(a, n, dt)
+        # + - * / max min of f32 operands round the same through f64; power does not, so it
+        # runs in the kernel's compute type (f32 for f32 and bf16 arrays)
+        ct = np.float32 if (dt != 1 and op == 6) else np.float64
+        x = self._load(a, n, dt).astype(ct)
         with np.errstate(all="ignore"):
+            if mode != 0 and dt != 1:
+                # the kernel converts the scalar once to its compute type
+                sc = np.float32(sc)
+            sc = ct(sc)
             if mode == 0:
-                r = self._BINARY[op](x, self._load(b, n, dt))
+                r = self._BINARY[op](x, self._load(b, n, dt).astype(ct))
             elif mode == 1:
                 r = self._BINARY[op](x, sc)
             else:
                 r = self._BINARY[op](sc, x)
-        self._store(y, r, dt)
+            self._store(y, r, dt)
 
     def cast(self, s, d, x, y, n) -> None:
         self.launches.append(("cast", s, d, n))
