@@ -122,6 +122,11 @@ BK_API int bk_fill(void* y, int64_t nbytes, uint64_t pattern, int pattern_bytes,
 // ---- reductions (reduce.hip) -------------------------------------------------------------
 // out: ONE double on the device.  workspace: BK_WS_REDUCE.
 // b is only read for kRedDot and kRedMaxAbsDiff (same length and dtype as a).
+// Every result is an f64 accumulation of the input widened to f64 (exactly, for
+// f32 and bf16): the square of f32 3e38 is the finite f64 value, not inf.
+// n = 0 (a, and b where it is read, still valid pointers) is kOk and stores the
+// op's identity: 0.0 for sum, square_sum, abs_sum and dot, -inf for max, +inf
+// for min, 0.0 for max_abs_diff; the workspace is left ready for the next launch.
 BK_API int bk_reduce(int op, int dtype, const void* a, const void* b, int64_t n, void* workspace, void* out,
                      hipStream_t stream);
 // sum (op 0) or square-sum (op 1) of the uniform [lo, hi) draw of n values

@@ -29,7 +29,10 @@ template <int OP> constexpr bool kTwoOperands = OP == kRedDot || OP == kRedMaxAb
 // length: 32 blocks per CU with 16 loads in flight per lane
 // (tools/probe/reduce_probe.hip: 1e8 f64 square-sum 152 -> 120 us, 5.2 ->
 // 6.6 TB/s, with non-temporal loads); the default grid is kRedBlocks,
-// BK_REDUCE_BLOCKS overrides it up to the workspace for sweeps.
+// BK_REDUCE_BLOCKS overrides it, any count from 1 up to the workspace, for
+// sweeps and tests.  (Until the knob was fixed it was rounded down to a
+// multiple of 256 blocks: the sweep rows labelled 384 and 640 below ran 256
+// and 512, profiles/INDEX.md.)
 // 512 blocks (2 per CU, 8 waves, 16 x 16-B loads in flight per lane):
 // tools/reduce_sweep.py on MI355X, 1e8 f64 square-sum, median of 20 --
 // grid-stride layout 167 / 135 / 141 / 154 / 164 / 178 us at 256 / 512 / 768 /
@@ -55,6 +58,19 @@ inline int64_t env_int(const char* name, int64_t dflt) {
   const char* e = getenv(name);
   const long long v = e ? atoll(e) : 0;
   return v > 0 ? (int64_t)v : dflt;
+}
+// a grid knob (BK_REDUCE_BLOCKS, BK_RANDRED_BLOCKS): the most blocks a launch
+// may have, any value from 1 to kRedMaxBlocks (the workspace holds that many
+// partials); anything else = default
+inline int64_t grid_knob(const char* name, int64_t dflt) {
+  const int64_t v = env_int(name, dflt);
+  return v <= kRedMaxBlocks ? v : dflt;
+}
+// min(the blocks `lanes` lanes of work need, the knob), at least one (n = 0
+// still launches: the fold writes the op's identity)
+inline unsigned grid_blocks(int64_t lanes, int64_t knob) {
+  const int64_t need = (lanes + kRedBlock - 1) / kRedBlock;
+  return (unsigned)(need < 1 ? 1 : need < knob ? need : knob);
 }
 
 template <typename T> __device__ __forceinline__ double to_f64(T v);
@@ -276,7 +292,8 @@ __global__ __launch_bounds__(kRedBlock) void reduce_chunked(const T* __restrict_
 // us per-wave contiguous, 139-141 us with grid-strided pieces (STRIDED), both
 // at 256 blocks; slower at 512+ (profiles/archive/r4_reduce_layout_sweep.jsonl).  A lab
 // layout (BK_REDUCE_LAYOUT=ldsdma / ldsdma_stride), exact against fp64 numpy
-// (tools/probe/reduce_layout_check.py).  Only the issuing wave reads a slot, so
+// (tests/test_reduce_gpu.py, one child process per layout).  Only the
+// issuing wave reads a slot, so
 // no barrier orders the ring: vmcnt before the read, lgkmcnt(0) before the
 // slot's next fill.  The DMA is inline asm so the compiler neither tracks it
 // nor inserts its own vmcnt(0) ahead of every LDS read (the GEMM's reason,
@@ -424,12 +441,9 @@ __global__ __launch_bounds__(kRedBlock) void rand_reduce_f32(int64_t n, uint32_t
 template <typename T, int OP>
 int launch_reduce(const void* a, const void* b, int64_t n, double* workspace, double* out, hipStream_t s) {
   constexpr int N = 16 / sizeof(T);
-  int64_t lanes_needed = (n / N + 3) / 4;  // 4 vectors per lane minimum before adding blocks
-  static const int64_t red_blocks = env_int("BK_REDUCE_BLOCKS", kRedBlocks) <= kRedMaxBlocks
-                                        ? env_int("BK_REDUCE_BLOCKS", kRedBlocks)
-                                        : kRedBlocks;
-  unsigned g = stream_grid(lanes_needed > 0 ? lanes_needed : 1, kRedBlock, (int)(red_blocks / kNumCU));
-  if (g > (unsigned)red_blocks) g = (unsigned)red_blocks;  // the workspace holds kRedMaxBlocks partials
+  const int64_t lanes_needed = (n / N + 3) / 4;  // 4 vectors per lane minimum before adding blocks
+  static const int64_t red_blocks = grid_knob("BK_REDUCE_BLOCKS", kRedBlocks);
+  const unsigned g = grid_blocks(lanes_needed, red_blocks);
   unsigned* ticket = reinterpret_cast<unsigned*>(workspace + kRedMaxBlocks);
   static const bool chunked = getenv("BK_REDUCE_LAYOUT") && !strcmp(getenv("BK_REDUCE_LAYOUT"), "chunk");
   static const bool ldsdma = getenv("BK_REDUCE_LAYOUT") && !strcmp(getenv("BK_REDUCE_LAYOUT"), "ldsdma");
@@ -704,12 +718,9 @@ BK_API int bk_rand_reduce(int op, int dtype, int64_t n, uint64_t seed, uint64_t 
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
   const int64_t units = dtype == kF64 ? (n + 1) / 2 : (n + 3) / 4;
   // fixed grid for a given n: results are reproducible run to run
-  // (BK_RANDRED_BLOCKS: lab override of the grid cap, <= kRedMaxBlocks)
-  static const int64_t max_blocks = env_int("BK_RANDRED_BLOCKS", kRandRedMaxBlocks) <= kRedMaxBlocks
-                                        ? env_int("BK_RANDRED_BLOCKS", kRandRedMaxBlocks)
-                                        : kRandRedMaxBlocks;
-  unsigned g = stream_grid(units > 0 ? (units + 7) / 8 : 1, kRedBlock, (int)(max_blocks / kNumCU));
-  if (g > (unsigned)max_blocks) g = (unsigned)max_blocks;
+  // (BK_RANDRED_BLOCKS: lab override of the grid cap, 1 to kRedMaxBlocks blocks)
+  static const int64_t max_blocks = grid_knob("BK_RANDRED_BLOCKS", kRandRedMaxBlocks);
+  const unsigned g = grid_blocks((units + 7) / 8, max_blocks);
   double* ws = (double*)workspace;
   unsigned* t = reinterpret_cast<unsigned*>(ws + kRedMaxBlocks);
   double* o = (double*)out;
