@@ -95,6 +95,7 @@ SIGNATURES = {
     "bk_event_destroy": ([c_vp], c_int),
     "bk_rand_uniform": ([c_vp, c_i64, c_int, c_u64, c_u64, c_d, c_d, c_vp], c_int),
     "bk_rand_normal": ([c_vp, c_i64, c_int, c_u64, c_u64, c_d, c_d, c_vp], c_int),
+    "bk_rand_dist": ([c_int, c_vp, c_i64, c_int, c_u64, c_u64, c_d, c_d, c_vp], c_int),
     "bk_unary": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp], c_int),
     "bk_binary": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_vp, c_i64, c_vp], c_int),
     "bk_cast": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp], c_int),

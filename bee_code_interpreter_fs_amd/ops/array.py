@@ -44,7 +44,8 @@ from typing import Any, Optional, Sequence, Tuple
 
 from ._lazy import is_integer, is_number, np, numpy_loaded, scalar
 from ._native import DTYPE_CODES, DTYPE_SIZES, BeekernError, QuotaExceeded  # noqa: F401
-from .driver import make_driver
+from .driver import (DIST_BETA, DIST_CAUCHY, DIST_EXPONENTIAL, DIST_GAMMA, DIST_GUMBEL, DIST_LAPLACE, DIST_LOGISTIC,
+                     DIST_LOGNORMAL, DIST_PARETO, DIST_RAYLEIGH, DIST_STUDENT_T, DIST_WEIBULL, make_driver)
 
 Shape = Tuple[int, ...]
 
@@ -1436,6 +1437,80 @@ class Generator:
     def normal(self, loc=0.0, scale=1.0, size=None, dtype="float64") -> DeviceArray:
         return self._draw(1, loc, scale, size, dtype)
 
+    # ---- the distributions of bk_rand_dist (csrc/kernels/random.hip): numpy's names and defaults --------
+    def _dist(self, kind: int, p0: float, p1: float, size, dtype, per: int = 0) -> DeviceArray:
+        """A materialised draw of distribution ``kind``.  per: elements a counter yields -- 0 for the
+        packing of the uniform draws (2 f64 / 4 f32), 1 for the rejection family (a substream each)."""
+        shape = _shape_of(size)
+        dt = normalize_dtype(dtype)
+        if dt == "bfloat16":  # the f32 draw, rounded
+            return self._dist(kind, p0, p1, shape, "float32", per).astype("bfloat16")
+        if dt not in ("float32", "float64"):
+            raise TypeError(f"random draws are float32, float64 or bfloat16, not {dt}")
+        n = int(math.prod(shape)) if shape else 1
+        off = self._advance(n, per or (2 if dt == "float64" else 4))
+        out = DeviceArray(shape, dt)
+        driver().rand_dist(kind, out.ptr, out.size, out.code, self._seed, off, float(p0), float(p1))
+        return out
+
+    def exponential(self, scale=1.0, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_EXPONENTIAL, _param("scale", scale, 0), 0.0, size, dtype)
+
+    def standard_exponential(self, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_EXPONENTIAL, 1.0, 0.0, size, dtype)
+
+    def laplace(self, loc=0.0, scale=1.0, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_LAPLACE, _param("loc", loc), _param("scale", scale, 0), size, dtype)
+
+    def logistic(self, loc=0.0, scale=1.0, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_LOGISTIC, _param("loc", loc), _param("scale", scale, 0), size, dtype)
+
+    def gumbel(self, loc=0.0, scale=1.0, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_GUMBEL, _param("loc", loc), _param("scale", scale, 0), size, dtype)
+
+    def rayleigh(self, scale=1.0, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_RAYLEIGH, _param("scale", scale, 0), 0.0, size, dtype)
+
+    def weibull(self, a, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_WEIBULL, _param("a", a, 1), 0.0, size, dtype)
+
+    def pareto(self, a, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_PARETO, _param("a", a, 1), 0.0, size, dtype)
+
+    def standard_cauchy(self, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_CAUCHY, 0.0, 1.0, size, dtype)
+
+    def lognormal(self, mean=0.0, sigma=1.0, size=None, dtype="float64") -> DeviceArray:
+        """exp of the ``normal(mean, sigma)`` draw at the same seed and counter."""
+        return self._dist(DIST_LOGNORMAL, _param("mean", mean), _param("sigma", sigma, 0), size, dtype)
+
+    def gamma(self, shape, scale=1.0, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_GAMMA, _param("shape", shape, 1), _param("scale", scale, 0), size, dtype, per=1)
+
+    def standard_gamma(self, shape, size=None, dtype="float64") -> DeviceArray:
+        return self.gamma(shape, 1.0, size, dtype)
+
+    def chisquare(self, df, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_GAMMA, 0.5 * _param("df", df, 1), 2.0, size, dtype, per=1)
+
+    def beta(self, a, b, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_BETA, _param("a", a, 1), _param("b", b, 1), size, dtype, per=1)
+
+    def standard_t(self, df, size=None, dtype="float64") -> DeviceArray:
+        return self._dist(DIST_STUDENT_T, _param("df", df, 1), 0.0, size, dtype, per=1)
+
+
+def _param(name: str, v, rule: int = -1) -> float:
+    """A distribution's parameter as a finite float; rule 0: >= 0, 1: > 0 (ValueError in numpy's words)."""
+    f = float(v)
+    if not math.isfinite(f):
+        raise ValueError(f"{name} must be finite")
+    if rule == 0 and f < 0.0:
+        raise ValueError(f"{name} < 0")
+    if rule == 1 and f <= 0.0:
+        raise ValueError(f"{name} <= 0")
+    return f
+
 
 def _shape_of(size) -> Shape:
     if size is None:
@@ -1467,6 +1542,25 @@ class _RandomModule:
     def uniform(self, low=0.0, high=1.0, size=None, dtype="float64"): return self.gen.uniform(low, high, size, dtype)
     def normal(self, loc=0.0, scale=1.0, size=None, dtype="float64"): return self.gen.normal(loc, scale, size, dtype)
     def standard_normal(self, size=None, dtype="float64"): return self.gen.standard_normal(size, dtype)
+    def exponential(self, scale=1.0, size=None, dtype="float64"): return self.gen.exponential(scale, size, dtype)
+    def standard_exponential(self, size=None, dtype="float64"): return self.gen.standard_exponential(size, dtype)
+    def laplace(self, loc=0.0, scale=1.0, size=None, dtype="float64"): return self.gen.laplace(loc, scale, size, dtype)
+    def gumbel(self, loc=0.0, scale=1.0, size=None, dtype="float64"): return self.gen.gumbel(loc, scale, size, dtype)
+    def rayleigh(self, scale=1.0, size=None, dtype="float64"): return self.gen.rayleigh(scale, size, dtype)
+    def weibull(self, a, size=None, dtype="float64"): return self.gen.weibull(a, size, dtype)
+    def pareto(self, a, size=None, dtype="float64"): return self.gen.pareto(a, size, dtype)
+    def standard_cauchy(self, size=None, dtype="float64"): return self.gen.standard_cauchy(size, dtype)
+    def lognormal(self, mean=0.0, sigma=1.0, size=None, dtype="float64"):
+        return self.gen.lognormal(mean, sigma, size, dtype)
+
+    def logistic(self, loc=0.0, scale=1.0, size=None, dtype="float64"):
+        return self.gen.logistic(loc, scale, size, dtype)
+
+    def gamma(self, shape, scale=1.0, size=None, dtype="float64"): return self.gen.gamma(shape, scale, size, dtype)
+    def standard_gamma(self, shape, size=None, dtype="float64"): return self.gen.standard_gamma(shape, size, dtype)
+    def chisquare(self, df, size=None, dtype="float64"): return self.gen.chisquare(df, size, dtype)
+    def beta(self, a, b, size=None, dtype="float64"): return self.gen.beta(a, b, size, dtype)
+    def standard_t(self, df, size=None, dtype="float64"): return self.gen.standard_t(df, size, dtype)
 
 
 random = _RandomModule()

@@ -42,6 +42,10 @@ _STATS_SCRATCH_BYTES = _STATS_COUNTS_AT + MAX_BINS * 8
 # the kernels' scratch workspaces: enum BkWorkspace of csrc/kernels/beekern.h
 WS_REDUCE, WS_REDUCE_AXIS, WS_AXIS_STAT, WS_COMPRESS, WS_SELECT, WS_HISTOGRAM, WS_COUNT = range(7)
 
+# the distributions of bk_rand_dist: enum BkRandDist of csrc/kernels/beekern.h
+(DIST_EXPONENTIAL, DIST_LAPLACE, DIST_LOGISTIC, DIST_GUMBEL, DIST_RAYLEIGH, DIST_WEIBULL, DIST_PARETO, DIST_CAUCHY,
+ DIST_LOGNORMAL, DIST_GAMMA, DIST_BETA, DIST_STUDENT_T, DIST_COUNT) = range(13)
+
 
 class NativeDriver:
     name = "native"
@@ -88,6 +92,10 @@ class NativeDriver:
     def rand(self, kind: int, h: int, n: int, dt: int, seed: int, off: int, a: float, b: float) -> None:
         fn = self.lib.bk_rand_uniform if kind == 0 else self.lib.bk_rand_normal
         check(fn(_vp(h), n, dt, seed, off, a, b, self.stream), "bk_rand")
+
+    def rand_dist(self, kind: int, h: int, n: int, dt: int, seed: int, off: int, p0: float, p1: float) -> None:
+        """n draws of the distribution ``kind`` (a DIST_* code) into h; f32 / f64."""
+        check(self.lib.bk_rand_dist(kind, _vp(h), n, dt, seed, off, p0, p1, self.stream), "bk_rand_dist")
 
     def unary(self, op: int, dt: int, x: int, y: int, n: int) -> None:
         check(self.lib.bk_unary(op, dt, _vp(x), _vp(y), n, self.stream), "bk_unary")
@@ -281,7 +289,7 @@ def _info_dict(v, arch: str) -> dict:
 
 (HELLO, ALLOC, FREE, WRITE, READ, RAND, UNARY, BINARY, CAST, FILL, REDUCE, GEMM, TRANSPOSE, SYNC, MEMSTATS, INFO,
  COPY, RAND_REDUCE, ALLOC_AT, REDUCE_AXIS, GEMM_FP, COMPARE, COMPARE_COUNT, MASK_LOGICAL, WHERE,
- COMPRESS, SELECT, HISTOGRAM, BROADCAST, AXIS_STAT) = range(1, 31)
+ COMPRESS, SELECT, HISTOGRAM, BROADCAST, AXIS_STAT, RAND_DIST) = range(1, 32)
 _HDR = struct.Struct("<IIQ")
 _NO_REPLY = 1  # request flag: no response unless a later request collects an error
 _RHDR = struct.Struct("<iIQ")
@@ -483,6 +491,9 @@ class BrokerDriver:
 
     def rand(self, kind, h, n, dt, seed, off, a, b) -> None:
         self._post(RAND, struct.pack("<IIQqQQdd", kind, dt, h, n, seed & 0xFFFFFFFFFFFFFFFF, off, a, b))
+
+    def rand_dist(self, kind, h, n, dt, seed, off, p0, p1) -> None:
+        self._post(RAND_DIST, struct.pack("<IIQqQQdd", kind, dt, h, n, seed & 0xFFFFFFFFFFFFFFFF, off, p0, p1))
 
     def unary(self, op, dt, x, y, n) -> None:
         self._post(UNARY, struct.pack("<IIQQq", op, dt, x, y, n))

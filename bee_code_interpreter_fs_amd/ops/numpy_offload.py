@@ -5,7 +5,14 @@ for every request) the sandbox patches ``numpy.random``'s legacy module
 functions -- ``rand``, ``random`` / ``random_sample`` / ``ranf`` /
 ``sample``, ``uniform``, ``randn``, ``standard_normal``, ``normal`` -- and
 the ``random`` / ``uniform`` / ``normal`` / ``standard_normal`` methods of
-``numpy.random.default_rng()`` Generators, so a draw of at least ``BEE_NUMPY_OFFLOAD_MIN`` elements (default 2**20) returns
+``numpy.random.default_rng()`` Generators, and on both the continuous
+distributions ``exponential`` / ``standard_exponential``, ``laplace``,
+``logistic``, ``gumbel``, ``rayleigh``, ``weibull``, ``pareto``,
+``standard_cauchy``, ``lognormal``, ``standard_gamma`` / ``gamma``,
+``chisquare``, ``beta`` and ``standard_t`` (scalar parameters inside the
+distribution's domain; array parameters, ``out=`` and every integer-valued
+distribution -- ``poisson``, ``binomial``, ``integers``, ``choice`` -- stay
+numpy's own), so a draw of at least ``BEE_NUMPY_OFFLOAD_MIN`` elements (default 2**20) returns
 an :class:`OffloadArray`: a device array (Philox4x32-10 on the GPU,
 ``ops/array.py``) that numpy functions and operators dispatch on through
 ``__array_ufunc__`` / ``__array_function__`` (``ops/npinterop.py``).  The
@@ -487,6 +494,86 @@ def _wrap_standard_normal(orig):
     return standard_normal
 
 
+# The other continuous distributions (csrc/kernels/random.hip bk_rand_dist), by numpy's name: the parameters
+# ahead of ``size`` as (name, default, rule) -- rule -1: any finite value, 0: >= 0, 1: > 0 -- and, for the
+# Generator methods that take them, the keywords after ``size``.  The device generator's methods carry the
+# same names (ops/array.py).
+_REQUIRED = object()
+_DISTS = {
+    "exponential": ((("scale", 1.0, 0),), ()),
+    "standard_exponential": ((), ("dtype", "method", "out")),
+    "laplace": ((("loc", 0.0, -1), ("scale", 1.0, 0)), ()),
+    "logistic": ((("loc", 0.0, -1), ("scale", 1.0, 0)), ()),
+    "gumbel": ((("loc", 0.0, -1), ("scale", 1.0, 0)), ()),
+    "rayleigh": ((("scale", 1.0, 0),), ()),
+    "weibull": ((("a", _REQUIRED, 1),), ()),
+    "pareto": ((("a", _REQUIRED, 1),), ()),
+    "standard_cauchy": ((), ()),
+    "lognormal": ((("mean", 0.0, -1), ("sigma", 1.0, 0)), ()),
+    "standard_gamma": ((("shape", _REQUIRED, 1),), ("dtype", "out")),
+    "gamma": ((("shape", _REQUIRED, 1), ("scale", 1.0, 0)), ()),
+    "chisquare": ((("df", _REQUIRED, 1),), ()),
+    "beta": ((("a", _REQUIRED, 1), ("b", _REQUIRED, 1)), ()),
+    "standard_t": ((("df", _REQUIRED, 1),), ()),
+}
+
+
+def _device_draw(dev_gen, name: str, args, kwargs, generator: bool):
+    """The draw ``name(*args, **kwargs)`` on the device generator, or None where numpy's own call must
+    run: a small or odd size, a parameter that is not a plain finite scalar inside the domain (arrays,
+    ``shape == 0`` and what numpy refuses, with its own error), ``out=``, another dtype, a call that does
+    not bind."""
+    params, extras = _DISTS[name]
+    names = [p[0] for p in params] + ["size"] + (list(extras) if generator else [])
+    if len(args) > len(names) or any(k not in names[len(args):] for k in kwargs):
+        return None
+    given = dict(zip(names, args), **kwargs)
+    if not _big(given.get("size")):
+        return None
+    values = []
+    for pname, default, rule in params:
+        v = given.get(pname, default)
+        if v is _REQUIRED or not _scalar(v) or not math.isfinite(float(v)):
+            return None
+        if (rule == 0 and float(v) < 0.0) or (rule == 1 and float(v) <= 0.0):
+            return None
+        values.append(float(v))
+    if given.get("out") is not None or given.get("method", "zig") not in ("zig", "inv"):
+        return None
+    try:
+        dtype = np.dtype(given.get("dtype", np.float64)).name
+    except TypeError:
+        return None
+    if dtype not in ("float32", "float64"):
+        return None
+    return OffloadArray(getattr(dev_gen, name)(*values, _shape(given["size"]), dtype))
+
+
+def _wrap_dist(name):
+    def wrap(orig):
+        @functools.wraps(orig)
+        def draw(*args, **kwargs):
+            r = _device_draw(_gen(), name, args, kwargs, generator=False)
+            return orig(*args, **kwargs) if r is None else r
+
+        return draw
+
+    return wrap
+
+
+def _generator_dist(name):
+    """The method ``name`` of the patched Generator class."""
+    base = getattr(np.random.Generator, name)
+
+    def draw(self, *args, **kwargs):
+        r = _device_draw(self._bee_dev, name, args, kwargs, generator=True)
+        return base(self, *args, **kwargs) if r is None else r
+
+    draw.__name__ = draw.__qualname__ = name
+    draw.__doc__ = base.__doc__
+    return draw
+
+
 def _wrap_seed(orig):
     @functools.wraps(orig)
     def seed(seed=None):
@@ -548,6 +635,8 @@ def _generator_class():
                 return OffloadArray(self._bee_dev.normal(float(loc), float(scale), _shape(size)))
             return super().normal(loc, scale, size)
 
+    for name in _DISTS:
+        setattr(Generator, name, _generator_dist(name))
     Generator.__module__ = "numpy.random"
     _GENCLS.append(Generator)
     return Generator
@@ -579,6 +668,7 @@ _WRAPPERS = {
     "standard_normal": _wrap_standard_normal,
     "seed": _wrap_seed,
     "default_rng": _wrap_default_rng,
+    **{name: _wrap_dist(name) for name in _DISTS},
 }
 
 

@@ -53,7 +53,8 @@ class HipDevice final : public broker::Device {
   X(gemm_bf16_tn) X(gemm_bf16_nn) X(gemm_fp) X(gemm_f32x6) X(transpose)                                              \
   X(compare) X(compare_count) X(mask_logical) X(where) X(compress) /* boolean masks (mask.hip) */                    \
   X(select) X(histogram)                                           /* order statistics, histograms (stats.hip) */    \
-  X(broadcast) X(axis_stat)                                        /* matrix against vector, axis statistics (axis.hip) */
+  X(broadcast) X(axis_stat)                                        /* matrix against vector, axis statistics (axis.hip) */ \
+  X(rand_dist)                                                     /* continuous distributions (random.hip) */
   struct Bk {
 #define X(name) decltype(&bk_##name) name = nullptr;
     BEE_BK_ENTRY_POINTS(X)
@@ -454,6 +455,11 @@ class HipDevice final : public broker::Device {
     return timed(s, pick(s, short_bytes(n, elem_bytes(dt))), [&](hipStream_t q) {
       return kind == 0 ? bk.rand_uniform(y, n, (int)dt, seed, off, a, b, q) : bk.rand_normal(y, n, (int)dt, seed, off, a, b, q);
     });
+  }
+  int rand_dist(uint32_t kind, void* y, int64_t n, uint32_t dt, uint64_t seed, uint64_t off, double p0, double p1,
+                void* s) override {
+    return timed(s, pick(s, short_bytes(n, elem_bytes(dt))),
+                 [&](hipStream_t q) { return bk.rand_dist((int)kind, y, n, (int)dt, seed, off, p0, p1, q); });
   }
   int unary(uint32_t op, uint32_t dt, const void* x, void* y, int64_t n, void* s) override {
     return timed(s, pick(s, short_bytes(n, elem_bytes(dt), 2)),

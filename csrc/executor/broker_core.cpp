@@ -17,7 +17,7 @@ const char* op_name(uint32_t op) {
                                       "bk.memstats", "bk.info",  "bk.copy",   "bk.rand_reduce", "bk.alloc_at",
                                       "bk.reduce_axis", "bk.gemm_fp", "bk.compare", "bk.compare_count",
                                       "bk.mask_logical", "bk.where", "bk.compress", "bk.select", "bk.histogram",
-                                      "bk.broadcast", "bk.axis_stat"};
+                                      "bk.broadcast", "bk.axis_stat", "bk.rand_dist"};
   return op < sizeof(names) / sizeof(names[0]) ? names[op] : names[0];
 }
 
@@ -247,6 +247,21 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
         return kBadHandle;
       if (!will_write(b, 0, need)) return kLaunchFailed;
       return dev_.rand(kind, b->ptr, n, dt, seed, off, a, bb, stream_);
+    }
+    case kRandDist: {
+      const uint32_t kind = r.get<uint32_t>(), dt = r.get<uint32_t>();
+      const uint64_t h = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      const uint64_t seed = r.get<uint64_t>(), off = r.get<uint64_t>();
+      const double p0 = r.get<double>(), p1 = r.get<double>();
+      if (!r.ok) return kProtocol;
+      // what the distribution cannot take is refused here, before the device is asked
+      if (kind >= kDistCount || dt > 1 || !dist_params_ok(kind, p0, p1)) return kBadArgument;
+      uint64_t need;
+      Buf* b = lookup(h);
+      if (n < 0 || !mul_ok((uint64_t)n, dtype_size(dt), &need) || !b || need > b->size) return kBadHandle;
+      if (!will_write(b, 0, need)) return kLaunchFailed;
+      return dev_.rand_dist(kind, b->ptr, n, dt, seed, off, p0, p1, stream_);
     }
     case kUnary: {
       const uint32_t uop = r.get<uint32_t>(), dt = r.get<uint32_t>();

@@ -60,8 +60,31 @@ enum Op : uint32_t {
   //                 op 0 max, 1 min, 2 variance, 3 standard deviation along axis 0 (y: cols elements of dt)
   //                 or 1 (rows elements); divisor: the variance's n - ddof, finite and > 0 for every op
   kBroadcast, kAxisStat,
+  // continuous distributions (csrc/kernels/random.hip bk_rand_dist), kRand's layout:
+  //   kRandDist     u32 kind | u32 dt | u64 h | i64 n | u64 seed | u64 off | f64 p0 | f64 p1
+  //                 kind 0 exponential (p0 scale), 1 laplace, 2 logistic, 3 gumbel (p0 loc, p1 scale), 4 rayleigh
+  //                 (p0 scale), 5 weibull, 6 pareto (p0 a), 7 cauchy (p0 loc, p1 scale), 8 lognormal (p0 mean,
+  //                 p1 sigma), 9 gamma (p0 shape, p1 scale), 10 beta (p0 a, p1 b), 11 student t (p0 df); dt 0 f32 /
+  //                 1 f64 only; p0 and p1 finite, scale and sigma >= 0, shape, a, b and df > 0 (kBadArgument
+  //                 otherwise); h holds n elements (kBadHandle otherwise, as kRand)
+  kRandDist,
   kOpCount
 };
+constexpr uint32_t kDistCount = 12;  // = BK_DIST_COUNT of csrc/kernels/beekern.h
+// p0, p1 finite and inside the domain of distribution `kind` (the rule of bk_rand_dist)
+inline bool dist_params_ok(uint32_t kind, double p0, double p1) {
+  // (a NaN fails every comparison; the upper bound refuses inf)
+  const auto finite = [](double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; };
+  if (!finite(p0) || !finite(p1)) return false;
+  switch (kind) {
+    case 0: case 4: return p0 >= 0.0;                          // scale
+    case 1: case 2: case 3: case 7: case 8: return p1 >= 0.0;  // loc | mean, scale | sigma
+    case 5: case 6: case 11: return p0 > 0.0;                  // a, df
+    case 9: return p0 > 0.0 && p1 >= 0.0;                      // shape, scale
+    case 10: return p0 > 0.0 && p1 > 0.0;                      // a, b
+  }
+  return false;
+}
 constexpr uint32_t kMaxRanks = 32;   // = kMaxRanks, kMaxBins of csrc/kernels/stats.hip
 constexpr uint32_t kMaxBins = 4096;
 constexpr uint32_t kDtBool = 6;  // not a dtype_size() code: the mask ops size masks as n bytes themselves
@@ -181,6 +204,10 @@ class Device {
     return kBadArgument;
   }
   virtual int axis_stat(uint32_t, uint32_t, const void*, void*, int64_t, int64_t, int64_t, uint32_t, double, void*) {
+    return kBadArgument;
+  }
+  // n draws of a continuous distribution (bk_rand_dist); the session has validated kind, dt and the parameters
+  virtual int rand_dist(uint32_t, void*, int64_t, uint32_t, uint64_t, uint64_t, double, double, void*) {
     return kBadArgument;
   }
   virtual int transpose(int sdt, int ddt, const void* in, void* out, int rows, int cols, int ldi, int ldo, void* s) = 0;

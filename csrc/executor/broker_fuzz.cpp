@@ -76,6 +76,47 @@ class HostDevice final : public Device {
     touch_w(y, (uint64_t)n * dtype_size(dt), (uint8_t)seed);
     return 0;
   }
+  // Philox4x32-10 (csrc/kernels/bk_philox.hpp) on the host
+  static void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
+    for (int r = 0; r < 10; ++r) {
+      const uint64_t p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+      const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+      c[1] = (uint32_t)p1;
+      c[3] = (uint32_t)p0;
+      c[0] = n0;
+      c[2] = n2;
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+  }
+  // bk_rand_dist: every byte of the n elements written; the exponential
+  // (kind 0) with the kernel's own values -- scale * -log1p(-u) of the open
+  // 53-bit / 24-bit uniforms of the dist streams -- so a read-back is checked
+  int rand_dist(uint32_t kind, void* y, int64_t n, uint32_t dt, uint64_t seed, uint64_t off, double p0, double p1,
+                void*) override {
+    if (kind >= kDistCount || dt > 1 || n < 0 || !dist_params_ok(kind, p0, p1)) return kBadArgument;
+    if (kind != 0) {
+      touch_w(y, (uint64_t)n * dtype_size(dt), (uint8_t)kind);
+      return 0;
+    }
+    const int per = dt == 1 ? 2 : 4;
+    for (int64_t i = 0; i < n; i += per) {
+      const uint64_t ctr = off + (uint64_t)(i / per);
+      uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), dt == 1 ? 0x64697374u : 0x64697375u, 0u};
+      philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+      for (int j = 0; j < per && i + j < n; ++j) {
+        if (dt == 1) {
+          const double u = ((double)(c[2 * j] >> 5) * 67108864.0 + (double)((c[2 * j + 1] >> 6) | 1u)) *
+                           (1.0 / 9007199254740992.0);
+          set<double>(y, i + j, p0 * -std::log1p(-u));
+        } else {
+          const float u = (float)((c[j] >> 8) | 1u) * (1.0f / 16777216.0f);
+          set<float>(y, i + j, (float)p0 * -std::log1p(-u));
+        }
+      }
+    }
+    return 0;
+  }
   int unary(uint32_t op, uint32_t dt, const void* x, void* y, int64_t n, void*) override {
     if (op > 31 || dt > 2) return kBadArgument;
     copy(y, x, (uint64_t)n * dtype_size(dt));

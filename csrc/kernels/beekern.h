@@ -104,6 +104,31 @@ BK_API int bk_rand_uniform(void* out, int64_t n, int dtype, uint64_t seed, uint6
                            hipStream_t stream);
 BK_API int bk_rand_normal(void* out, int64_t n, int dtype, uint64_t seed, uint64_t offset, double mean, double std,
                           hipStream_t stream);
+// the continuous distributions of bk_rand_dist and what p0, p1 mean for each (an unused one is passed as 0)
+enum BkRandDist {
+  BK_DIST_EXPONENTIAL = 0,  // p0 scale
+  BK_DIST_LAPLACE,          // p0 loc, p1 scale
+  BK_DIST_LOGISTIC,         // p0 loc, p1 scale
+  BK_DIST_GUMBEL,           // p0 loc, p1 scale
+  BK_DIST_RAYLEIGH,         // p0 scale
+  BK_DIST_WEIBULL,          // p0 a
+  BK_DIST_PARETO,           // p0 a (numpy's Lomax form)
+  BK_DIST_CAUCHY,           // p0 loc, p1 scale
+  BK_DIST_LOGNORMAL,        // p0 mean, p1 sigma of the underlying normal
+  BK_DIST_GAMMA,            // p0 shape, p1 scale
+  BK_DIST_BETA,             // p0 a, p1 b
+  BK_DIST_STUDENT_T,        // p0 df
+  BK_DIST_COUNT
+};
+// n draws of `kind` at (seed, offset); dtype kF64 or kF32.  Kinds 0-7 are one transform of an open-interval
+// uniform and consume a counter per 2 f64 / 4 f32 elements, as bk_rand_uniform (streams of their own); lognormal
+// is exp of bk_rand_normal's value for the same (seed, offset, mean, sigma); gamma, beta and student t are
+// rejection samplers in f64 (the f32 result is the f64 value rounded once) that consume one counter per element:
+// element i depends on (seed, offset + i) alone.  No value is inf or NaN for exponential .. cauchy, lognormal
+// within exp's range.  kBadArgument before any launch for an unknown kind, another dtype, a null out, n < 0, a
+// non-finite p0 or p1, or a parameter outside its domain (scale, sigma >= 0; shape, a, b, df > 0); n = 0 is kOk.
+BK_API int bk_rand_dist(int kind, void* out, int64_t n, int dtype, uint64_t seed, uint64_t offset, double p0, double p1,
+                        hipStream_t stream);
 
 // ---- elementwise (elementwise.hip) ------------------------------------------------------
 // f64 computes in f64; f32 and bf16 compute in f32 (bf16 rounds once on store).

@@ -41,7 +41,26 @@ __device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
 }
 __device__ __forceinline__ float u24(uint32_t a) { return (float)(a >> 8) * (1.0f / 16777216.0f); }
 
+// the same integers with the low bit set, scaled: uniforms on the OPEN interval
+// (0, 1) -- 2^-53 .. 1 - 2^-53 and 2^-24 .. 1 - 2^-24, every value exact -- for
+// the transforms that take a log of u or of 1 - u (a counter stream cannot
+// redraw u == 0 as numpy does)
+__device__ __forceinline__ double u53_open(uint32_t a, uint32_t b) {
+  return ((double)(a >> 5) * 67108864.0 + (double)((b >> 6) | 1u)) * (1.0 / 9007199254740992.0);
+}
+__device__ __forceinline__ float u24_open(uint32_t a) { return (float)((a >> 8) | 1u) * (1.0f / 16777216.0f); }
+// one word as a uniform on (0, 1): (w + 1/2) 2^-32, exact in f64
+__device__ __forceinline__ double u32_open(uint32_t w) { return ((double)w + 0.5) * (1.0 / 4294967296.0); }
+
 // stream tags: distinct counter words per distribution
 constexpr uint32_t kTagUniformF64 = 0x62656b65u, kTagUniformF32 = 0x62656b66u;
+constexpr uint32_t kTagNormalF32 = 0x6e6f726du, kTagNormalF64 = 0x6e6f726eu;
+// the one-uniform transforms of bk_rand_dist (exponential .. cauchy), per precision
+constexpr uint32_t kTagDistF64 = 0x64697374u, kTagDistF32 = 0x64697375u;
+// the rejection family: element i's substream is (offset + i, tag, attempt).
+// Two gamma substreams (beta's X and Y), student t's normal, and the uniform
+// that boosts a shape < 1 draw (tag + kTagBoost of its gamma substream)
+constexpr uint32_t kTagGammaX = 0x67616d30u, kTagGammaY = 0x67616d31u, kTagStudentN = 0x67616d32u;
+constexpr uint32_t kTagBoost = 0x10u;
 
 }  // namespace bk

@@ -232,6 +232,52 @@ def axis_rows():
         del x, y, vc, vr, tx, tvc, tvr
 
 
+def dist_rows():
+    """The continuous distributions (csrc/kernels/random.hip bk_rand_dist), n = 1e8,
+    f64 and f32, driver calls into one buffer: `python tools/bench_kernels.py dist`
+    (profiles/dist_kernels.jsonl).  Each beside a yardstick measured in the same
+    run: the one-uniform transforms beside bk_rand_uniform of the dtype (the
+    write-bound floor), lognormal and the rejection kinds beside bk_rand_normal;
+    torch's device samplers on a buffer of the same size are the outside reference."""
+    from bee_code_interpreter_fs_amd.ops import driver as D
+    from bee_code_interpreter_fs_amd.ops.array import driver
+
+    bk.init()
+    emit(kernel="device", **bk.device_info())
+    drv = driver()
+    n = 10**8
+    one_uniform = [("exponential", D.DIST_EXPONENTIAL, 2.0, 0.0), ("laplace", D.DIST_LAPLACE, 1.0, 0.5),
+                   ("logistic", D.DIST_LOGISTIC, -1.0, 2.0), ("gumbel", D.DIST_GUMBEL, 0.5, 1.5),
+                   ("rayleigh", D.DIST_RAYLEIGH, 1.5, 0.0), ("weibull(1.7)", D.DIST_WEIBULL, 1.7, 0.0),
+                   ("pareto(3)", D.DIST_PARETO, 3.0, 0.0), ("cauchy", D.DIST_CAUCHY, 0.0, 1.0)]
+    rejection = [("gamma(2.5)", D.DIST_GAMMA, 2.5, 1.0), ("gamma(0.3)", D.DIST_GAMMA, 0.3, 1.0),
+                 ("beta(2, 5)", D.DIST_BETA, 2.0, 5.0), ("student_t(5)", D.DIST_STUDENT_T, 5.0, 0.0)]
+    for dtype, esize in (("float64", 8), ("float32", 4)):
+        x = bk.empty(n, dtype)
+        tx = torch.empty(n, dtype=torch.float64 if esize == 8 else torch.float32, device="cuda")
+
+        def row(kernel, fn, timer="bk", **kw):
+            ms, mn, mx = spread(fn, timer, reps=10, warmup=2)
+            emit(kernel=f"{kernel} [{dtype}]", n=n, ms=ms, min_ms=mn, max_ms=mx, GBps=n * esize / ms / 1e6, **kw)
+            return ms, mn, mx
+
+        u_ms, u_mn, u_mx = row("rand_uniform", lambda: drv.rand(0, x.ptr, n, x.code, 1, 0, 0.0, 1.0))
+        n_ms, n_mn, n_mx = row("rand_normal", lambda: drv.rand(1, x.ptr, n, x.code, 1, 0, 0.0, 1.0))
+        for name, kind, p0, p1 in one_uniform:
+            ms, _, _ = row(name, lambda: drv.rand_dist(kind, x.ptr, n, x.code, 1, 0, p0, p1))
+            emit(kernel=f"{name} vs rand_uniform [{dtype}]", ratio=ms / u_ms, within_uniform_spread=bool(ms <= u_mx))
+        ms, _, _ = row("lognormal", lambda: drv.rand_dist(D.DIST_LOGNORMAL, x.ptr, n, x.code, 1, 0, 0.0, 1.0))
+        emit(kernel=f"lognormal vs rand_normal [{dtype}]", ratio=ms / n_ms, within_normal_spread=bool(ms <= n_mx))
+        for name, kind, p0, p1 in rejection:
+            ms, _, _ = row(name, lambda: drv.rand_dist(kind, x.ptr, n, x.code, 1, 0, p0, p1))
+            emit(kernel=f"{name} vs rand_normal [{dtype}]", ratio=ms / n_ms)
+        row("torch exponential_", lambda: tx.exponential_(), "torch")
+        row("torch log_normal_", lambda: tx.log_normal_(), "torch")
+        alpha = torch.full_like(tx, 2.5)
+        row("torch._standard_gamma(2.5)", lambda: torch._standard_gamma(alpha), "torch")
+        del alpha, tx, x
+
+
 def emit(**kw):
     print(json.dumps(kw), flush=True)
 
@@ -317,5 +363,5 @@ def main():
 
 
 if __name__ == "__main__":
-    modes = {"masks": mask_rows, "stats": stats_rows, "axis": axis_rows}
+    modes = {"masks": mask_rows, "stats": stats_rows, "axis": axis_rows, "dist": dist_rows}
     modes[sys.argv[1]]() if len(sys.argv) == 2 and sys.argv[1] in modes else main()
