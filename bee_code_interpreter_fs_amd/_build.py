@@ -68,7 +68,7 @@ def _targets() -> List[Target]:
             compiler=HIPCC,
             compile_flags=HIP_FLAGS,
             link_flags=[f"--offload-arch={ARCH}", "-shared", "-fPIC"],
-            headers=[os.path.join(k, f) for f in ("beekern.h", "bk_common.hpp", "bk_philox.hpp", "bk_ticket.hpp", "bk_binary_op.hpp", "gemm256_impl.hpp", "gemm256w4_impl.hpp")],
+            headers=[os.path.join(k, f) for f in ("beekern.h", "bk_common.hpp", "bk_dispatch.hpp", "bk_philox.hpp", "bk_ticket.hpp", "bk_binary_op.hpp", "gemm256_impl.hpp", "gemm256w4_impl.hpp")],
             hip=True,
         ),
     ]
@@ -178,7 +178,7 @@ def _targets() -> List[Target]:
                 # 256 accumulators + fragments otherwise bounce through AGPR moves
                 compile_flags=HIP_FLAGS + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                 link_flags=[f"--offload-arch={ARCH}", "-shared", "-fPIC"],
-                headers=[os.path.join(k, "beekern.h"), os.path.join(k, "bk_common.hpp"), os.path.join(k, "gemm256_impl.hpp"), os.path.join(k, "gemm256w4_impl.hpp")],
+                headers=[os.path.join(k, "beekern.h"), os.path.join(k, "bk_common.hpp"), os.path.join(k, "bk_dispatch.hpp"), os.path.join(k, "gemm256_impl.hpp"), os.path.join(k, "gemm256w4_impl.hpp")],
                 hip=True,
                 optional=True,
             )

@@ -40,7 +40,7 @@ STATUS = {
     5: "device not initialized",
 }
 
-# dtype codes shared with csrc/kernels/bk_common.hpp
+# dtype codes shared with csrc/kernels/bk_dispatch.hpp
 DTYPE_CODES = {"float32": 0, "float64": 1, "bfloat16": 2, "float16": 3, "int32": 4, "int64": 5, "bool": 6}
 DTYPE_SIZES = {"float32": 4, "float64": 8, "bfloat16": 2, "float16": 2, "int32": 4, "int64": 8, "bool": 1}
 

@@ -50,7 +50,6 @@ inline int log2_ceil(int64_t n, int cap_log) {
 
 // ---- bk_broadcast ----------------------------------------------------------------
 constexpr int kBcBlock = 256;
-constexpr int kBcUnroll = 4;  // = kEwUnroll (elementwise.hip): accesses in flight per lane
 
 // y[r][c] = a[r][c] OP v[c] (KIND 0) or a[r][c] OP v[r] (KIND 1); SWAP: v OP a.
 // `cvecs` row pieces of VEC elements; lg = log2 of the tile's column lanes.
@@ -59,7 +58,7 @@ template <typename T, int OP, int KIND, bool SWAP, int VEC, bool NT>
 __global__ __launch_bounds__(kBcBlock) void broadcast_kernel(const T* a, const T* __restrict__ v, T* y, int64_t rows,
                                                             int64_t cvecs, int64_t lda, int64_t ldy, int lg) {
   using P = Pack<T, VEC>;
-  constexpr int U = kBcUnroll;
+  constexpr int U = kStreamUnroll;
   const int cw = 1 << lg, rl_n = kBcBlock >> lg;
   const int cl = threadIdx.x & (cw - 1), rl = threadIdx.x >> lg;
   const int64_t cstep = (int64_t)gridDim.x * cw;
@@ -127,34 +126,17 @@ int launch_broadcast(const T* a, const T* v, T* y, int64_t rows, int64_t cols, i
   const int64_t cap = (int64_t)kNumCU * kStreamBlocksPerCU;
   int64_t gc = (cvecs + cw - 1) / cw;
   if (gc > cap) gc = cap;
-  int64_t gr = (rows + kBcUnroll * rl_n - 1) / (kBcUnroll * rl_n);
+  int64_t gr = (rows + kStreamUnroll * rl_n - 1) / (kStreamUnroll * rl_n);
   if (gr > cap / gc) gr = cap / gc > 0 ? cap / gc : 1;
   const dim3 grid((unsigned)gc, (unsigned)gr);
-  const bool nt = stream_nt(rows * cols * (int64_t)sizeof(T));
-  if (vec) {
-    if (nt) broadcast_kernel<T, OP, KIND, SWAP, N, true><<<grid, kBcBlock, 0, s>>>(a, v, y, rows, cvecs, lda, ldy, lg);
-    else broadcast_kernel<T, OP, KIND, SWAP, N, false><<<grid, kBcBlock, 0, s>>>(a, v, y, rows, cvecs, lda, ldy, lg);
-  } else {
-    broadcast_kernel<T, OP, KIND, SWAP, 1, false><<<grid, kBcBlock, 0, s>>>(a, v, y, rows, cvecs, lda, ldy, lg);
-  }
+  if (vec)
+    return dispatch_flag(stream_nt(rows * cols * (int64_t)sizeof(T)), [&](auto nt) {
+      broadcast_kernel<T, OP, KIND, SWAP, N, decltype(nt)::value>
+          <<<grid, kBcBlock, 0, s>>>(a, v, y, rows, cvecs, lda, ldy, lg);
+      return launch_status();
+    });
+  broadcast_kernel<T, OP, KIND, SWAP, 1, false><<<grid, kBcBlock, 0, s>>>(a, v, y, rows, cvecs, lda, ldy, lg);
   return launch_status();
-}
-
-template <typename T, int... OPS>
-int dispatch_broadcast(int op, int kind, bool swapped, const void* a, const void* v, void* y, int64_t rows, int64_t cols,
-                       int64_t lda, int64_t ldy, hipStream_t s, std::integer_sequence<int, OPS...>) {
-  int rc = kBadArgument;
-  auto one = [&](auto opc) {
-    constexpr int OP = decltype(opc)::value;
-    const T *pa = (const T*)a, *pv = (const T*)v;
-    T* py = (T*)y;
-    if (kind == 0) rc = swapped ? launch_broadcast<T, OP, 0, true>(pa, pv, py, rows, cols, lda, ldy, s)
-                                : launch_broadcast<T, OP, 0, false>(pa, pv, py, rows, cols, lda, ldy, s);
-    else rc = swapped ? launch_broadcast<T, OP, 1, true>(pa, pv, py, rows, cols, lda, ldy, s)
-                      : launch_broadcast<T, OP, 1, false>(pa, pv, py, rows, cols, lda, ldy, s);
-  };
-  ((op == OPS ? (one(std::integral_constant<int, OPS>{}), 0) : 0), ...);
-  return rc;
 }
 
 // bytes spanned by a rows x cols matrix of row stride ld; false if that wraps
@@ -174,14 +156,10 @@ enum StatOp : int { kStatMax = 0, kStatMin, kStatVar, kStatStd, kStatCount };
 // what a kernel accumulates: max, min, a sum (the mean pass), squared deviations
 enum Mode : int { kMax = 0, kMin, kSum, kSqDev };
 
-// partials (chunks x columns), the column means between the two launches of a
-// column variance, one ticket per column block -- in the sizes of reduce.hip's
-// axis workspace (bk_ticket.hpp)
-constexpr int64_t kWsDoubles = kAxisWsDoubles;
-constexpr int64_t kTickets = kAxisTickets;
-constexpr int kColWaves = 16;
-
-template <typename T> struct alignas(16) V16 { T v[16 / sizeof(T)]; };
+// The workspace: partials (chunks x columns, kAxisWsDoubles), the column means
+// between the two launches of a column variance (as many), one ticket per
+// column block (kAxisTickets) -- the sizes of reduce.hip's axis workspace
+// (bk_ticket.hpp).
 
 template <int MODE> __device__ __forceinline__ double init() {
   if constexpr (MODE == kMax) return -INFINITY;
@@ -399,14 +377,14 @@ template <typename T>
 ColPlan plan_cols(const T* x, int64_t rows, int64_t cols, int64_t ld) {
   constexpr int V = 16 / sizeof(T);
   ColPlan p;
-  p.vec = cols % V == 0 && ld % V == 0 && ((uintptr_t)x & 15) == 0 && (cols + 16 * V - 1) / (16 * V) <= kTickets;
+  p.vec = cols % V == 0 && ld % V == 0 && ((uintptr_t)x & 15) == 0 && (cols + 16 * V - 1) / (16 * V) <= kAxisTickets;
   p.lgc = log2_ceil(cols / V, 4);
   const int64_t strip = (int64_t)V << p.lgc;
   const int64_t col_blocks = p.vec ? (cols + strip - 1) / strip : (cols + 255) / 256;
   // (a table of one or two strips: 512 blocks, two per CU, where launch_axis's
   // 128 would leave half the CUs without one)
   int64_t chunks = (p.vec ? (col_blocks <= 2 ? 512 : 128) : 1024) / col_blocks;
-  if (chunks * cols > kWsDoubles) chunks = kWsDoubles / cols;
+  if (chunks * cols > kAxisWsDoubles) chunks = kAxisWsDoubles / cols;
   const int64_t min_rows = p.vec ? 1024 : 32;
   if (chunks > (rows + min_rows - 1) / min_rows) chunks = (rows + min_rows - 1) / min_rows;
   if (chunks < 1) chunks = 1;
@@ -420,7 +398,7 @@ ColPlan plan_cols(const T* x, int64_t rows, int64_t cols, int64_t ld) {
 template <typename T, int MODE>
 int launch_cols(const ColPlan& p, const T* x, int64_t rows, int64_t cols, int64_t ld, double* ws, const double* means,
                 void* out, double divisor, bool root, hipStream_t s) {
-  unsigned* tickets = reinterpret_cast<unsigned*>(ws + 2 * kWsDoubles);
+  unsigned* tickets = reinterpret_cast<unsigned*>(ws + 2 * kAxisWsDoubles);
   if (p.vec)
     col_stat_v<T, MODE><<<p.grid, kColWaves * 64, 0, s>>>(x, rows, cols, ld, p.per, ws, tickets, means, out, divisor, root,
                                                           p.lgc);
@@ -442,12 +420,12 @@ int launch_stat(int op, const T* x, int64_t rows, int64_t cols, int64_t ld, int 
     return kBadArgument;
   }
   const ColPlan p = plan_cols<T>(x, rows, cols, ld);
-  if (p.grid.x > kTickets) return kBadArgument;
+  if (p.grid.x > kAxisTickets) return kBadArgument;
   if (op == kStatMax) return launch_cols<T, kMax>(p, x, rows, cols, ld, ws, nullptr, out, 1.0, false, s);
   if (op == kStatMin) return launch_cols<T, kMin>(p, x, rows, cols, ld, ws, nullptr, out, 1.0, false, s);
   // two launches on one stream: the f64 column means into the workspace, then
   // the squared deviations from them
-  double* means = ws + kWsDoubles;
+  double* means = ws + kAxisWsDoubles;
   const int rc = launch_cols<T, kSum>(p, x, rows, cols, ld, ws, nullptr, means, (double)rows, false, s);
   if (rc != kOk) return rc;
   return launch_cols<T, kSqDev>(p, x, rows, cols, ld, ws, means, out, divisor, op == kStatStd, s);
@@ -457,8 +435,8 @@ int launch_stat(int op, const T* x, int64_t rows, int64_t cols, int64_t ld, int 
 
 // partials and column means, then the tickets
 WsLayout axis_stat_ws_layout() {
-  const int64_t doubles = 2 * axis::kWsDoubles * (int64_t)sizeof(double);
-  const int64_t tickets = axis::kTickets * (int64_t)sizeof(unsigned);
+  const int64_t doubles = 2 * kAxisWsDoubles * (int64_t)sizeof(double);
+  const int64_t tickets = kAxisTickets * (int64_t)sizeof(unsigned);
   return {doubles + tickets, doubles, tickets};
 }
 
@@ -481,10 +459,17 @@ BK_API int bk_broadcast(int op, int dtype, int kind, int swapped, const void* a,
     return kBadArgument;
   if (axis::overlap(y, ny, v, nv)) return kBadArgument;
   if (!(y == a && ldy == lda) && axis::overlap(y, ny, a, na)) return kBadArgument;
-  using Ops = std::make_integer_sequence<int, kBinCount>;
-  if (dtype == kF64)
-    return axis::dispatch_broadcast<double>(op, kind, swapped != 0, a, v, y, rows, cols, lda, ldy, stream, Ops{});
-  return axis::dispatch_broadcast<float>(op, kind, swapped != 0, a, v, y, rows, cols, lda, ldy, stream, Ops{});
+  return dispatch_dtype<double, float>(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return dispatch_op<kBinCount>(op, [&](auto opc) {
+      return dispatch_flag(kind == 0, [&](auto along_rows) {
+        return dispatch_flag(swapped != 0, [&](auto swap) {
+          return axis::launch_broadcast<T, decltype(opc)::value, decltype(along_rows)::value ? 0 : 1, decltype(swap)::value>(
+              (const T*)a, (const T*)v, (T*)y, rows, cols, lda, ldy, stream);
+        });
+      });
+    });
+  });
 }
 
 BK_API int bk_axis_stat(int op, int dtype, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis,
@@ -494,7 +479,7 @@ BK_API int bk_axis_stat(int op, int dtype, const void* x, int64_t rows, int64_t 
     return kBadArgument;
   if ((op == axis::kStatVar || op == axis::kStatStd) && !(divisor > 0.0 && divisor <= 1.7976931348623157e308))
     return kBadArgument;
-  if (axis == 0 && cols > axis::kWsDoubles) return kBadArgument;  // > 262144 columns: reduce a transposed view instead
+  if (axis == 0 && cols > kAxisWsDoubles) return kBadArgument;  // > 262144 columns: reduce a transposed view instead
   if (((uintptr_t)x | (uintptr_t)out) & (uintptr_t)(dtype_size(dtype) - 1)) return kBadArgument;
   if (dtype == kF64)
     return axis::launch_stat<double>(op, (const double*)x, rows, cols, ld, axis, divisor, (double*)out, (double*)ws, stream);

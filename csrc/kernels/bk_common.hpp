@@ -15,7 +15,8 @@
 #include <utility>
 #include <type_traits>
 
-#include "beekern.h"  // BK_API, the limits and one declaration of every entry point
+#include "beekern.h"      // BK_API, the limits and one declaration of every entry point
+#include "bk_dispatch.hpp"  // Status, DType and the launch dispatch on op, flag and dtype codes
 
 namespace bk {
 
@@ -23,18 +24,8 @@ constexpr int kWave = 64;
 constexpr int kNumCU = 256;       // MI355X
 constexpr int kNumXCD = 8;        // 8 XCDs x 32 CUs, private L2 each
 
-enum Status : int {
-  kOk = 0,
-  kBadArgument = 1,
-  kLaunchFailed = 2,
-  kOutOfMemory = 3,
-  kQuotaExceeded = 4,
-  kNotInitialized = 5,
-};
-
-// kBool: numpy's bool, one byte per element -- kernels write exactly 0 or 1
-// and read any non-zero byte as true (mask.hip)
-enum DType : int { kF32 = 0, kF64 = 1, kBF16 = 2, kF16 = 3, kI32 = 4, kI64 = 5, kBool = 6 };
+static_assert(std::is_same<uint16_t, unsigned short>::value && std::is_same<uint8_t, unsigned char>::value,
+              "bk_dispatch.hpp spells the bf16 and bool element types without <stdint.h>");
 
 inline int dtype_size(int dt) {
   switch (dt) {
@@ -93,6 +84,18 @@ WsLayout histogram_ws_layout();    // stats.hip
 constexpr int64_t kStreamNtBytes = 256ll << 20;
 inline bool stream_nt(int64_t bytes) { return bytes >= kStreamNtBytes; }
 
+// 16 bytes of T: what a lane moves per access
+template <typename T>
+struct alignas(16) V16 {
+  static constexpr int N = 16 / sizeof(T);
+  T v[N];
+};
+
+// 16-B accesses in flight per lane and operand before the first store, in the
+// streaming kernels that write as much as they read (elementwise.hip,
+// mask.hip's compare and where, axis.hip's broadcast)
+constexpr int kStreamUnroll = 4;
+
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 
 template <bool NT, typename V>
@@ -150,6 +153,12 @@ __device__ __forceinline__ T block_sum(T v) {
 __device__ __forceinline__ float bf16_bits_to_float(uint16_t b) {
   return __uint_as_float(((uint32_t)b) << 16);
 }
+
+// an element as f64, exactly (uint16_t: bf16 bits)
+template <typename T> __device__ __forceinline__ double widen(T v);
+template <> __device__ __forceinline__ double widen<double>(double v) { return v; }
+template <> __device__ __forceinline__ double widen<float>(float v) { return (double)v; }
+template <> __device__ __forceinline__ double widen<uint16_t>(uint16_t v) { return (double)bf16_bits_to_float(v); }
 
 // round-to-nearest-even; NaN stays NaN via the hardware cvt (MI355X microarch,
 // correctness boundaries row on f32->bf16).

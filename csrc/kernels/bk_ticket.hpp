@@ -1,5 +1,6 @@
-// Single-launch completion tickets, shared by the reductions (reduce.hip) and
-// the mask kernels (mask.hip).
+// Single-launch completion tickets and the grid and workspace numbers that go
+// with them, shared by the reductions (reduce.hip), the mask kernels
+// (mask.hip) and the axis statistics (axis.hip); stats.hip takes the tickets.
 //
 // Every block publishes its partial, then takes a ticket; the block holding
 // the last ticket folds the partials and re-arms the ticket for the next
@@ -30,11 +31,26 @@ constexpr int kRedBlock = 256;
 // the reduction workspace holds kRedMaxBlocks f64 partials, then the ticket
 // (its own 256 B): BK_WS_REDUCE
 constexpr int kRedMaxBlocks = 32768;
+// the default stage-1 grid of a reduction and of a count: 2 blocks per CU
+// (measured: reduce.hip); BK_REDUCE_BLOCKS overrides it for bk_reduce alone
+constexpr int kRedBlocks = 512;
 // the axis workspaces of reduce.hip and axis.hip: chunks x columns f64 partials
 // (which set the width limit of a column reduction), then one ticket per
 // column block (<= 2048 at 262144 columns)
 constexpr int64_t kAxisWsDoubles = BK_MAX_AXIS0_COLUMNS;
 constexpr int64_t kAxisTickets = 4096;
+// waves of a block of the 16-B column kernels (reduce.hip colsum_tile_v, axis.hip col_stat_v)
+constexpr int kColWaves = 16;
+
+// min(the blocks `lanes` lanes of work need, `cap`), at least one (n = 0
+// still launches: the fold writes the op's identity)
+inline unsigned grid_blocks(int64_t lanes, int64_t cap) {
+  const int64_t need = (lanes + kRedBlock - 1) / kRedBlock;
+  return (unsigned)(need < 1 ? 1 : need < cap ? need : cap);
+}
+
+// bk_reduce on a kBool mask: op 0 the count of non-zero bytes, 3 any, 4 all (mask.hip)
+int reduce_bool(int op, const void* a, int64_t n, void* workspace, void* out, hipStream_t stream);
 
 template <typename T>
 __device__ __forceinline__ void publish(T* p, T v) {

@@ -50,19 +50,11 @@ __device__ __forceinline__ C unary(C x) {
   else return x;
 }
 
-template <typename T>
-struct alignas(16) Vec {
-  static constexpr int N = 16 / sizeof(T);
-  T v[N];
-};
-
-constexpr int kEwUnroll = 4;  // 16-B loads in flight per lane before the first store
-
 template <typename T, int OP, bool NT>
 __global__ __launch_bounds__(256) void unary_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n) {
   using E = Elem<T>;
-  using V = Vec<T>;
-  constexpr int N = V::N, U = kEwUnroll;
+  using V = V16<T>;
+  constexpr int N = V::N, U = kStreamUnroll;
   const int64_t nvec = n / N;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -100,9 +92,9 @@ __global__ __launch_bounds__(256) void binary_kernel(const T* __restrict__ a, co
                                                      T* __restrict__ y, int64_t n) {
   using E = Elem<T>;
   using C = typename E::C;
-  using V = Vec<T>;
+  using V = V16<T>;
   constexpr int N = V::N;
-  constexpr int U = kEwUnroll;
+  constexpr int U = kStreamUnroll;
   const C sc = (C)s;
   const int64_t nvec = n / N;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -164,14 +156,14 @@ __global__ __launch_bounds__(256) void bool_cast_kernel(const uint8_t* __restric
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nvec = n / 16;
   for (int64_t i = tid; i < nvec; i += stride) {
-    const Vec<uint8_t> m = reinterpret_cast<const Vec<uint8_t>*>(x)[i];
-    constexpr int N = Vec<TO>::N;
+    const V16<uint8_t> m = reinterpret_cast<const V16<uint8_t>*>(x)[i];
+    constexpr int N = V16<TO>::N;
 #pragma unroll
     for (int q = 0; q < 16 / N; ++q) {
-      Vec<TO> o;
+      V16<TO> o;
 #pragma unroll
       for (int j = 0; j < N; ++j) o.v[j] = m.v[q * N + j] != 0 ? TO(1) : TO(0);
-      reinterpret_cast<Vec<TO>*>(y)[i * (16 / N) + q] = o;
+      reinterpret_cast<V16<TO>*>(y)[i * (16 / N) + q] = o;
     }
   }
   for (int64_t k = nvec * 16 + tid; k < n; k += stride) y[k] = x[k] != 0 ? TO(1) : TO(0);
@@ -192,46 +184,6 @@ __global__ __launch_bounds__(256) void fill_kernel(uint8_t* __restrict__ y, int6
   for (int64_t i = nvec * 16 + tid; i < nbytes; i += stride) y[i] = (uint8_t)(p >> (8 * (i % 8)));
 }
 
-// ---- host dispatch ---------------------------------------------------------
-template <typename T, int OP>
-int launch_unary_t(const void* x, void* y, int64_t n, hipStream_t s) {
-  const unsigned g = stream_grid((n + Vec<T>::N - 1) / Vec<T>::N, 256);
-  if (stream_nt(n * (int64_t)sizeof(T))) unary_kernel<T, OP, true><<<g, 256, 0, s>>>((const T*)x, (T*)y, n);
-  else unary_kernel<T, OP, false><<<g, 256, 0, s>>>((const T*)x, (T*)y, n);
-  return launch_status();
-}
-
-template <typename T, int... OPS>
-int dispatch_unary(int op, const void* x, void* y, int64_t n, hipStream_t s, std::integer_sequence<int, OPS...>) {
-  int rc = kBadArgument;
-  ((op == OPS ? (rc = launch_unary_t<T, OPS>(x, y, n, s), 0) : 0), ...);
-  return rc;
-}
-
-template <typename T, int OP, bool BS, bool REV>
-int launch_binary_t(const void* a, const void* b, double sc, void* y, int64_t n, hipStream_t s) {
-  const unsigned g = stream_grid((n + Vec<T>::N - 1) / Vec<T>::N, 256);
-  if (stream_nt(n * (int64_t)sizeof(T)))
-    binary_kernel<T, OP, BS, REV, true><<<g, 256, 0, s>>>((const T*)a, (const T*)b, sc, (T*)y, n);
-  else
-    binary_kernel<T, OP, BS, REV, false><<<g, 256, 0, s>>>((const T*)a, (const T*)b, sc, (T*)y, n);
-  return launch_status();
-}
-
-template <typename T, int... OPS>
-int dispatch_binary(int op, int mode, const void* a, const void* b, double sc, void* y, int64_t n, hipStream_t s,
-                    std::integer_sequence<int, OPS...>) {
-  int rc = kBadArgument;
-  auto one = [&](auto opc) {
-    constexpr int OP = decltype(opc)::value;
-    if (mode == 0) rc = launch_binary_t<T, OP, false, false>(a, b, sc, y, n, s);
-    else if (mode == 1) rc = launch_binary_t<T, OP, true, false>(a, b, sc, y, n, s);
-    else rc = launch_binary_t<T, OP, true, true>(a, b, sc, y, n, s);
-  };
-  ((op == OPS ? (one(std::integral_constant<int, OPS>{}), 0) : 0), ...);
-  return rc;
-}
-
 }  // namespace bk
 
 using namespace bk;
@@ -240,13 +192,16 @@ using namespace bk;
 BK_API int bk_unary(int op, int dtype, const void* x, void* y, int64_t n, hipStream_t stream) {
   if (!x || !y || n < 0 || op < 0 || op >= kUnaryCount) return kBadArgument;
   if (n == 0) return kOk;
-  using Ops = std::make_integer_sequence<int, kUnaryCount>;
-  switch (dtype) {
-    case kF32: return dispatch_unary<float>(op, x, y, n, stream, Ops{});
-    case kF64: return dispatch_unary<double>(op, x, y, n, stream, Ops{});
-    case kBF16: return dispatch_unary<uint16_t>(op, x, y, n, stream, Ops{});
-  }
-  return kBadArgument;
+  return dispatch_dtype<float, double, uint16_t>(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    const unsigned g = stream_grid((n + V16<T>::N - 1) / V16<T>::N, 256);
+    return dispatch_op<kUnaryCount>(op, [&](auto opc) {
+      return dispatch_flag(stream_nt(n * (int64_t)sizeof(T)), [&](auto nt) {
+        unary_kernel<T, decltype(opc)::value, decltype(nt)::value><<<g, 256, 0, stream>>>((const T*)x, (T*)y, n);
+        return launch_status();
+      });
+    });
+  });
 }
 
 BK_API int bk_binary(int op, int dtype, int mode, const void* a, const void* b, double scalar, void* y, int64_t n,
@@ -254,13 +209,24 @@ BK_API int bk_binary(int op, int dtype, int mode, const void* a, const void* b, 
   if (!a || !y || n < 0 || op < 0 || op >= kBinCount || mode < 0 || mode > 2 || (mode == 0 && !b))
     return kBadArgument;
   if (n == 0) return kOk;
-  using Ops = std::make_integer_sequence<int, kBinCount>;
-  switch (dtype) {
-    case kF32: return dispatch_binary<float>(op, mode, a, b, scalar, y, n, stream, Ops{});
-    case kF64: return dispatch_binary<double>(op, mode, a, b, scalar, y, n, stream, Ops{});
-    case kBF16: return dispatch_binary<uint16_t>(op, mode, a, b, scalar, y, n, stream, Ops{});
-  }
-  return kBadArgument;
+  return dispatch_dtype<float, double, uint16_t>(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    const unsigned g = stream_grid((n + V16<T>::N - 1) / V16<T>::N, 256);
+    return dispatch_op<kBinCount>(op, [&](auto opc) {
+      // mode 0: b is an array; 1: the scalar on the right; 2: the scalar on the left
+      return dispatch_flag(mode == 0, [&](auto b_array) {
+        return dispatch_flag(mode != 2, [&](auto a_left) {
+          return dispatch_flag(stream_nt(n * (int64_t)sizeof(T)), [&](auto nt) {
+            constexpr bool BS = !decltype(b_array)::value, REV = !decltype(a_left)::value;
+            if constexpr (BS || !REV)  // (no mode swaps two arrays)
+              binary_kernel<T, decltype(opc)::value, BS, REV, decltype(nt)::value>
+                  <<<g, 256, 0, stream>>>((const T*)a, (const T*)b, scalar, (T*)y, n);
+            return launch_status();
+          });
+        });
+      });
+    });
+  });
 }
 
 BK_API int bk_cast(int src_dtype, int dst_dtype, const void* x, void* y, int64_t n, hipStream_t stream) {

@@ -23,11 +23,6 @@ namespace mask {
 enum CompareOp : int { kLt = 0, kLe, kGt, kGe, kEq, kNe, kCmpCount };
 enum LogicalOp : int { kAnd = 0, kOr, kXor, kNot, kLogicalCount };
 
-template <typename T> __device__ __forceinline__ double widen(T v);
-template <> __device__ __forceinline__ double widen<double>(double v) { return v; }
-template <> __device__ __forceinline__ double widen<float>(float v) { return (double)v; }
-template <> __device__ __forceinline__ double widen<uint16_t>(uint16_t v) { return (double)bf16_bits_to_float(v); }
-
 template <int OP> __device__ __forceinline__ bool cmp(double a, double b) {
   if constexpr (OP == kLt) return a < b;
   else if constexpr (OP == kLe) return a <= b;
@@ -37,10 +32,6 @@ template <int OP> __device__ __forceinline__ bool cmp(double a, double b) {
   else return a != b;
 }
 
-template <typename T> struct alignas(16) V16 {
-  static constexpr int N = 16 / sizeof(T);
-  T v[N];
-};
 using MaskVec = V16<uint32_t>;  // 16 mask bytes
 
 // 0x01 in every byte of w that is non-zero (no carry crosses a byte: the low
@@ -54,13 +45,11 @@ __device__ __forceinline__ unsigned count_nz(const MaskVec& m) {
 
 // ---- compare -> mask ---------------------------------------------------------------
 // A lane's 16-B vector yields only 2 / 4 / 8 mask bytes.  The block stages
-// the mask bytes of one chunk (kCmpUnroll x 256 vectors) in LDS -- each lane
+// the mask bytes of one chunk (kStreamUnroll x 256 vectors) in LDS -- each lane
 // writes its vector's N bytes as one 2 / 4 / 8-byte LDS store -- and writes
 // them back out as coalesced 16-B global stores, so the main loop issues no
 // byte-sized global store and the loads stay lane-interleaved.  Two LDS
 // buffers: one barrier per chunk.
-constexpr int kCmpUnroll = 4;  // = kEwUnroll of elementwise.hip: 16-B loads in flight per operand
-
 template <int N> struct MaskPiece;  // the N mask bytes of one vector
 template <> struct MaskPiece<2> { using type = uint16_t; };
 template <> struct MaskPiece<4> { using type = uint32_t; };
@@ -70,7 +59,7 @@ template <typename T, int OP, bool SCALAR, bool NT>
 __global__ __launch_bounds__(256) void compare_kernel(const T* __restrict__ a, const T* __restrict__ b, double s,
                                                       uint8_t* __restrict__ y, int64_t n) {
   using V = V16<T>;
-  constexpr int N = V::N, U = kCmpUnroll;
+  constexpr int N = V::N, U = kStreamUnroll;
   using Piece = typename MaskPiece<N>::type;
   constexpr int kChunkBytes = U * 256 * N;       // mask bytes of one chunk
   constexpr int kChunkVecs = kChunkBytes / 16;   // 16-B mask stores of one chunk
@@ -124,10 +113,9 @@ __global__ __launch_bounds__(256) void compare_kernel(const T* __restrict__ a, c
 }
 
 // ---- counts: fused compare-count, and count / any / all of a mask ------------------
-// reduce.hip's stream (grid-stride, 512 blocks, 16-B loads in flight, f64
-// partials folded in index order by the last-ticket block).  Partial counts
+// reduce.hip's stream (grid-stride, kRedBlocks blocks, 16-B loads in flight,
+// f64 partials folded in index order by the last-ticket block).  Partial counts
 // are integers below 2^53: the result is exact whatever the order.
-constexpr int kCountBlocks = 512;  // = kRedBlocks (reduce.hip)
 
 enum CountKind : int { kCountCompare = 0, kCountCompareScalar, kCountMask };
 enum CountFinal : int { kFinalCount = 0, kFinalAny, kFinalAll };
@@ -220,12 +208,6 @@ __global__ __launch_bounds__(kRedBlock) void count_kernel(const T* __restrict__ 
   finish_count(block_sum_f64((double)c), n, final_op, partials, ticket, out);
 }
 
-inline unsigned count_grid(int64_t nvec) {
-  const int64_t lanes_needed = (nvec + 3) / 4;  // 4 vectors per lane before adding blocks (launch_reduce)
-  unsigned g = stream_grid(lanes_needed > 0 ? lanes_needed : 1, kRedBlock, kCountBlocks / kNumCU);
-  return g > (unsigned)kCountBlocks ? (unsigned)kCountBlocks : g;
-}
-
 template <typename T, int OP, int KIND>
 int launch_count(const void* a, const void* b, double s, int64_t n, int final_op, double* ws, double* out,
                  hipStream_t q) {
@@ -233,54 +215,29 @@ int launch_count(const void* a, const void* b, double s, int64_t n, int final_op
   constexpr int64_t esize = KIND == kCountMask ? 1 : (int64_t)sizeof(T);
   // two-operand streams keep 8 vectors of each operand in flight (the register budget of 16 of one)
   constexpr int U = KIND == kCountCompare ? 8 : 16;
-  const unsigned g = count_grid(n / N);
+  // 4 vectors per lane before adding blocks, as launch_reduce; the default grid whatever BK_REDUCE_BLOCKS says
+  const unsigned g = grid_blocks((n / N + 3) / 4, kRedBlocks);
   unsigned* ticket = reinterpret_cast<unsigned*>(ws + kRedMaxBlocks);
-  if (stream_nt(n * esize * (KIND == kCountCompare ? 2 : 1)))
-    count_kernel<T, OP, KIND, true, U><<<g, kRedBlock, 0, q>>>((const T*)a, (const T*)b, s, n, final_op, ws, ticket, out);
-  else
-    count_kernel<T, OP, KIND, false, U><<<g, kRedBlock, 0, q>>>((const T*)a, (const T*)b, s, n, final_op, ws, ticket, out);
-  return launch_status();
+  return dispatch_flag(stream_nt(n * esize * (KIND == kCountCompare ? 2 : 1)), [&](auto nt) {
+    count_kernel<T, OP, KIND, decltype(nt)::value, U>
+        <<<g, kRedBlock, 0, q>>>((const T*)a, (const T*)b, s, n, final_op, ws, ticket, out);
+    return launch_status();
+  });
 }
 
 template <typename T, int OP>
 int launch_compare(int mode, const void* a, const void* b, double s, void* y, int64_t n, hipStream_t q) {
   constexpr int N = 16 / (int)sizeof(T);
   // whole chunks per block: the grid never exceeds the chunk count by much
-  const int64_t chunks = (n / N) / (kCmpUnroll * 256);
+  const int64_t chunks = (n / N) / (kStreamUnroll * 256);
   const unsigned g = stream_grid((chunks > 0 ? chunks : 1) * 256, 256);
-  const bool nt = stream_nt(n * (int64_t)sizeof(T) * (mode == 0 ? 2 : 1));
-  const T* ap = (const T*)a;
-  const T* bp = (const T*)b;
-  uint8_t* yp = (uint8_t*)y;
-  if (mode == 0) {
-    if (nt) compare_kernel<T, OP, false, true><<<g, 256, 0, q>>>(ap, bp, s, yp, n);
-    else compare_kernel<T, OP, false, false><<<g, 256, 0, q>>>(ap, bp, s, yp, n);
-  } else {
-    if (nt) compare_kernel<T, OP, true, true><<<g, 256, 0, q>>>(ap, bp, s, yp, n);
-    else compare_kernel<T, OP, true, false><<<g, 256, 0, q>>>(ap, bp, s, yp, n);
-  }
-  return launch_status();
-}
-
-template <typename T, int... OPS>
-int dispatch_compare(int op, int mode, const void* a, const void* b, double s, void* y, int64_t n, hipStream_t q,
-                     std::integer_sequence<int, OPS...>) {
-  int rc = kBadArgument;
-  ((op == OPS ? (rc = launch_compare<T, OPS>(mode, a, b, s, y, n, q), 0) : 0), ...);
-  return rc;
-}
-
-template <typename T, int... OPS>
-int dispatch_compare_count(int op, int mode, const void* a, const void* b, double s, int64_t n, double* ws, double* out,
-                           hipStream_t q, std::integer_sequence<int, OPS...>) {
-  int rc = kBadArgument;
-  auto one = [&](auto opc) {
-    constexpr int OP = decltype(opc)::value;
-    rc = mode == 0 ? launch_count<T, OP, kCountCompare>(a, b, s, n, kFinalCount, ws, out, q)
-                   : launch_count<T, OP, kCountCompareScalar>(a, b, s, n, kFinalCount, ws, out, q);
-  };
-  ((op == OPS ? (one(std::integral_constant<int, OPS>{}), 0) : 0), ...);
-  return rc;
+  return dispatch_flag(mode == 0, [&](auto arrays) {
+    return dispatch_flag(stream_nt(n * (int64_t)sizeof(T) * (mode == 0 ? 2 : 1)), [&](auto nt) {
+      compare_kernel<T, OP, !decltype(arrays)::value, decltype(nt)::value>
+          <<<g, 256, 0, q>>>((const T*)a, (const T*)b, s, (uint8_t*)y, n);
+      return launch_status();
+    });
+  });
 }
 
 // ---- mask logic --------------------------------------------------------------------
@@ -336,11 +293,10 @@ __global__ __launch_bounds__(256) void logical_kernel(const uint8_t* __restrict_
 template <int OP>
 int launch_logical(const void* a, const void* b, void* y, int64_t n, hipStream_t q) {
   const unsigned g = stream_grid((n + 15) / 16, 256);
-  if (stream_nt(n))
-    logical_kernel<OP, true><<<g, 256, 0, q>>>((const uint8_t*)a, (const uint8_t*)b, (uint8_t*)y, n);
-  else
-    logical_kernel<OP, false><<<g, 256, 0, q>>>((const uint8_t*)a, (const uint8_t*)b, (uint8_t*)y, n);
-  return launch_status();
+  return dispatch_flag(stream_nt(n), [&](auto nt) {
+    logical_kernel<OP, decltype(nt)::value><<<g, 256, 0, q>>>((const uint8_t*)a, (const uint8_t*)b, (uint8_t*)y, n);
+    return launch_status();
+  });
 }
 
 // ---- where -------------------------------------------------------------------------
@@ -352,7 +308,7 @@ __global__ __launch_bounds__(256) void where_kernel(const uint8_t* __restrict__ 
                                                     const T* __restrict__ b, T sa, T sb, T* __restrict__ y,
                                                     int64_t n) {
   using V = V16<T>;
-  constexpr int N = V::N, U = kCmpUnroll;
+  constexpr int N = V::N, U = kStreamUnroll;
   using Piece = typename MaskPiece<N>::type;
   const int64_t nvec = n / N;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -399,24 +355,16 @@ template <typename T>
 int launch_where(const void* m, int flags, const void* a, const void* b, T sa, T sb, void* y, int64_t n,
                  hipStream_t q) {
   const unsigned g = stream_grid((n + V16<T>::N - 1) / V16<T>::N, 256);
-  const bool nt = stream_nt(n * (int64_t)sizeof(T));
-  const uint8_t* mp = (const uint8_t*)m;
-  const T* ap = (const T*)a;
-  const T* bp = (const T*)b;
-  T* yp = (T*)y;
-#define BK_WHERE(AS, BS)                                                                       \
-  do {                                                                                         \
-    if (nt) where_kernel<T, AS, BS, true><<<g, 256, 0, q>>>(mp, ap, bp, sa, sb, yp, n);        \
-    else where_kernel<T, AS, BS, false><<<g, 256, 0, q>>>(mp, ap, bp, sa, sb, yp, n);          \
-  } while (0)
-  switch (flags & 3) {
-    case 0: BK_WHERE(false, false); break;
-    case 1: BK_WHERE(true, false); break;
-    case 2: BK_WHERE(false, true); break;
-    default: BK_WHERE(true, true); break;
-  }
-#undef BK_WHERE
-  return launch_status();
+  // flags bit 0: A is the scalar sa, bit 1: B is the scalar sb
+  return dispatch_flag(!(flags & 2), [&](auto b_array) {
+    return dispatch_flag(!(flags & 1), [&](auto a_array) {
+      return dispatch_flag(stream_nt(n * (int64_t)sizeof(T)), [&](auto nt) {
+        where_kernel<T, !decltype(a_array)::value, !decltype(b_array)::value, decltype(nt)::value>
+            <<<g, 256, 0, q>>>((const uint8_t*)m, (const T*)a, (const T*)b, sa, sb, (T*)y, n);
+        return launch_status();
+      });
+    });
+  });
 }
 
 // host-side RNE f32 -> bf16 bits (NaN -> quiet NaN), as float_to_bf16_bits
@@ -582,11 +530,12 @@ int launch_compress(const void* x, const void* m, int64_t n, void* out, int64_t 
   unsigned long long* counts = (unsigned long long*)ws;
   unsigned long long* offsets = counts + kCzMaxBlocks;
   unsigned* ticket = reinterpret_cast<unsigned*>(offsets + kCzMaxBlocks);
-  if (stream_nt(n))
-    compress_count<true><<<plan.grid, kCzBlock, 0, q>>>((const uint8_t*)m, n, plan.per, counts, offsets, ticket);
-  else
-    compress_count<false><<<plan.grid, kCzBlock, 0, q>>>((const uint8_t*)m, n, plan.per, counts, offsets, ticket);
-  if (hipGetLastError() != hipSuccess) return kLaunchFailed;
+  const int rc = dispatch_flag(stream_nt(n), [&](auto nt) {
+    compress_count<decltype(nt)::value>
+        <<<plan.grid, kCzBlock, 0, q>>>((const uint8_t*)m, n, plan.per, counts, offsets, ticket);
+    return launch_status();
+  });
+  if (rc != kOk) return rc;
   compress_scatter<T><<<plan.grid, kCzBlock, 0, q>>>((const T*)x, (const uint8_t*)m, n, plan.per, offsets, (T*)out, cap);
   return launch_status();
 }
@@ -616,27 +565,26 @@ BK_API int bk_compare(int op, int dtype, int mode, const void* a, const void* b,
     return kBadArgument;
   if (dtype != kF32 && dtype != kF64 && dtype != kBF16) return kBadArgument;
   if (n == 0) return kOk;
-  using Ops = std::make_integer_sequence<int, kCmpCount>;
-  switch (dtype) {
-    case kF32: return dispatch_compare<float>(op, mode, a, b, scalar, mask_out, n, stream, Ops{});
-    case kF64: return dispatch_compare<double>(op, mode, a, b, scalar, mask_out, n, stream, Ops{});
-    default: return dispatch_compare<uint16_t>(op, mode, a, b, scalar, mask_out, n, stream, Ops{});
-  }
+  return dispatch_dtype<float, double, uint16_t>(dtype, [&](auto t) {
+    return dispatch_op<kCmpCount>(op, [&](auto opc) {
+      return launch_compare<typename decltype(t)::type, decltype(opc)::value>(mode, a, b, scalar, mask_out, n, stream);
+    });
+  });
 }
 
 BK_API int bk_compare_count(int op, int dtype, int mode, const void* a, const void* b, double scalar, int64_t n,
                             void* workspace, void* out, hipStream_t stream) {
   if (!a || !workspace || !out || n < 0 || op < 0 || op >= kCmpCount || mode < 0 || mode > 1 || (mode == 0 && !b))
     return kBadArgument;
-  using Ops = std::make_integer_sequence<int, kCmpCount>;
-  double* ws = (double*)workspace;
-  double* o = (double*)out;
-  switch (dtype) {
-    case kF32: return dispatch_compare_count<float>(op, mode, a, b, scalar, n, ws, o, stream, Ops{});
-    case kF64: return dispatch_compare_count<double>(op, mode, a, b, scalar, n, ws, o, stream, Ops{});
-    case kBF16: return dispatch_compare_count<uint16_t>(op, mode, a, b, scalar, n, ws, o, stream, Ops{});
-  }
-  return kBadArgument;
+  return dispatch_dtype<float, double, uint16_t>(dtype, [&](auto t) {
+    return dispatch_op<kCmpCount>(op, [&](auto opc) {
+      return dispatch_flag(mode == 0, [&](auto arrays) {
+        constexpr int KIND = decltype(arrays)::value ? kCountCompare : kCountCompareScalar;
+        return launch_count<typename decltype(t)::type, decltype(opc)::value, KIND>(
+            a, b, scalar, n, kFinalCount, (double*)workspace, (double*)out, stream);
+      });
+    });
+  });
 }
 
 BK_API int bk_mask_logical(int op, const void* a, const void* b, void* out, int64_t n, hipStream_t stream) {

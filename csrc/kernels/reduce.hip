@@ -16,7 +16,7 @@
 
 #include "bk_common.hpp"
 #include "bk_philox.hpp"
-#include "bk_ticket.hpp"  // kRedBlock, kRedMaxBlocks and the completion tickets
+#include "bk_ticket.hpp"  // kRedBlock, kRedBlocks, kRedMaxBlocks, grid_blocks and the completion tickets
 
 namespace bk {
 
@@ -28,7 +28,7 @@ template <int OP> constexpr bool kTwoOperands = OP == kRedDot || OP == kRedMaxAb
 // kRedMaxBlocks (bk_ticket.hpp) is the stage-1 grid cap and the workspace
 // length: 32 blocks per CU with 16 loads in flight per lane
 // (tools/probe/reduce_probe.hip: 1e8 f64 square-sum 152 -> 120 us, 5.2 ->
-// 6.6 TB/s, with non-temporal loads); the default grid is kRedBlocks,
+// 6.6 TB/s, with non-temporal loads); the default grid is kRedBlocks (bk_ticket.hpp),
 // BK_REDUCE_BLOCKS overrides it, any count from 1 up to the workspace, for
 // sweeps and tests.  (Until the knob was fixed it was rounded down to a
 // multiple of 256 blocks: the sweep rows labelled 384 and 640 below ran 256
@@ -44,7 +44,6 @@ template <int OP> constexpr bool kTwoOperands = OP == kRedDot || OP == kRedMaxAb
 // instead of 16 at 512 / 1024 / 2048 blocks: 137.7 / 164-167 / 166-172 us --
 // the grid (8 waves per CU), not the bytes in flight, sets the rate, and
 // ~5.8 TB/s (torch.sum's too) is this read stream's ceiling on these boxes
-constexpr int kRedBlocks = 512;
 constexpr int kRedUnroll = 16;
 // the fused RNG->reduce kernels are VALU-bound (80% of SIMD cycles issue
 // VALU, profiles/archive/r4_payload_kernels_pmc.csv): 8 blocks per CU (8 waves per
@@ -66,17 +65,6 @@ inline int64_t grid_knob(const char* name, int64_t dflt) {
   const int64_t v = env_int(name, dflt);
   return v <= kRedMaxBlocks ? v : dflt;
 }
-// min(the blocks `lanes` lanes of work need, the knob), at least one (n = 0
-// still launches: the fold writes the op's identity)
-inline unsigned grid_blocks(int64_t lanes, int64_t knob) {
-  const int64_t need = (lanes + kRedBlock - 1) / kRedBlock;
-  return (unsigned)(need < 1 ? 1 : need < knob ? need : knob);
-}
-
-template <typename T> __device__ __forceinline__ double to_f64(T v);
-template <> __device__ __forceinline__ double to_f64<double>(double v) { return v; }
-template <> __device__ __forceinline__ double to_f64<float>(float v) { return (double)v; }
-template <> __device__ __forceinline__ double to_f64<uint16_t>(uint16_t v) { return (double)bf16_bits_to_float(v); }
 
 template <int OP> __device__ __forceinline__ double red_init() {
   if constexpr (OP == kRedMax) return -INFINITY;
@@ -120,8 +108,6 @@ template <int OP> __device__ __forceinline__ double block_reduce(double v) {
   }
   return r;
 }
-
-template <typename T> struct alignas(16) V16 { T v[16 / sizeof(T)]; };
 
 // ---- single-launch completion (the tickets: bk_ticket.hpp) ----------------------
 // the fold of `count` partials into *out by the last block
@@ -174,8 +160,8 @@ __global__ __launch_bounds__(kRedBlock) void reduce_1pass(const T* __restrict__ 
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int j = 0; j < N; ++j) {
-        const double bj = kTwoOperands<OP> ? to_f64<T>(vb[u].v[j]) : 0.0;
-        acc[u] = red_combine<OP>(acc[u], red_map<OP>(to_f64<T>(va[u].v[j]), bj));
+        const double bj = kTwoOperands<OP> ? widen<T>(vb[u].v[j]) : 0.0;
+        acc[u] = red_combine<OP>(acc[u], red_map<OP>(widen<T>(va[u].v[j]), bj));
       }
   }
   // the rest in groups of 4 loads in flight: at 1e8 f64 on the capped grid a
@@ -193,8 +179,8 @@ __global__ __launch_bounds__(kRedBlock) void reduce_1pass(const T* __restrict__ 
     for (int u = 0; u < U2; ++u)
 #pragma unroll
       for (int j = 0; j < N; ++j) {
-        const double bj = kTwoOperands<OP> ? to_f64<T>(vb[u].v[j]) : 0.0;
-        acc[u] = red_combine<OP>(acc[u], red_map<OP>(to_f64<T>(va[u].v[j]), bj));
+        const double bj = kTwoOperands<OP> ? widen<T>(vb[u].v[j]) : 0.0;
+        acc[u] = red_combine<OP>(acc[u], red_map<OP>(widen<T>(va[u].v[j]), bj));
       }
   }
   for (; i < nvec; i += stride) {
@@ -203,13 +189,13 @@ __global__ __launch_bounds__(kRedBlock) void reduce_1pass(const T* __restrict__ 
     if constexpr (kTwoOperands<OP>) vb = reinterpret_cast<const V*>(b)[i];
 #pragma unroll
     for (int j = 0; j < N; ++j) {
-      const double bj = kTwoOperands<OP> ? to_f64<T>(vb.v[j]) : 0.0;
-      acc[0] = red_combine<OP>(acc[0], red_map<OP>(to_f64<T>(va.v[j]), bj));
+      const double bj = kTwoOperands<OP> ? widen<T>(vb.v[j]) : 0.0;
+      acc[0] = red_combine<OP>(acc[0], red_map<OP>(widen<T>(va.v[j]), bj));
     }
   }
   for (int64_t k = nvec * N + tid; k < n; k += stride) {
-    const double bk_ = kTwoOperands<OP> ? to_f64<T>(b[k]) : 0.0;
-    acc[0] = red_combine<OP>(acc[0], red_map<OP>(to_f64<T>(a[k]), bk_));
+    const double bk_ = kTwoOperands<OP> ? widen<T>(b[k]) : 0.0;
+    acc[0] = red_combine<OP>(acc[0], red_map<OP>(widen<T>(a[k]), bk_));
   }
   double v = acc[0];
 #pragma unroll
@@ -254,8 +240,8 @@ __global__ __launch_bounds__(kRedBlock) void reduce_chunked(const T* __restrict_
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int j = 0; j < N; ++j) {
-        const double bj = kTwoOperands<OP> ? to_f64<T>(vb[u].v[j]) : 0.0;
-        acc[u] = red_combine<OP>(acc[u], red_map<OP>(to_f64<T>(va[u].v[j]), bj));
+        const double bj = kTwoOperands<OP> ? widen<T>(vb[u].v[j]) : 0.0;
+        acc[u] = red_combine<OP>(acc[u], red_map<OP>(widen<T>(va[u].v[j]), bj));
       }
   }
   for (; i < v1; i += kRedBlock) {
@@ -264,15 +250,15 @@ __global__ __launch_bounds__(kRedBlock) void reduce_chunked(const T* __restrict_
     if constexpr (kTwoOperands<OP>) vb = ld16<NT>(reinterpret_cast<const V*>(b) + i);
 #pragma unroll
     for (int j = 0; j < N; ++j) {
-      const double bj = kTwoOperands<OP> ? to_f64<T>(vb.v[j]) : 0.0;
-      acc[0] = red_combine<OP>(acc[0], red_map<OP>(to_f64<T>(va.v[j]), bj));
+      const double bj = kTwoOperands<OP> ? widen<T>(vb.v[j]) : 0.0;
+      acc[0] = red_combine<OP>(acc[0], red_map<OP>(widen<T>(va.v[j]), bj));
     }
   }
   // the scalar tail (n % N elements) in the last block
   if (blockIdx.x == gridDim.x - 1)
     for (int64_t k = nvec * N + threadIdx.x; k < n; k += kRedBlock) {
-      const double bk_ = kTwoOperands<OP> ? to_f64<T>(b[k]) : 0.0;
-      acc[0] = red_combine<OP>(acc[0], red_map<OP>(to_f64<T>(a[k]), bk_));
+      const double bk_ = kTwoOperands<OP> ? widen<T>(b[k]) : 0.0;
+      acc[0] = red_combine<OP>(acc[0], red_map<OP>(widen<T>(a[k]), bk_));
     }
   double v = acc[0];
 #pragma unroll
@@ -342,7 +328,7 @@ __global__ __launch_bounds__(kRedBlock) void reduce_ldsdma(const T* __restrict__
   auto take = [&](double& r, int slot) {
     const V16<T> v = *reinterpret_cast<const V16<T>*>(mine + slot * 1024);
 #pragma unroll
-    for (int q = 0; q < N; ++q) r = red_combine<OP>(r, red_map<OP>(to_f64<T>(v.v[q]), 0.0));
+    for (int q = 0; q < N; ++q) r = red_combine<OP>(r, red_map<OP>(widen<T>(v.v[q]), 0.0));
   };
   const int64_t first = np < S ? np : S;
   for (int64_t j = 0; j < first; ++j) dma_piece<NT>(src + j * step, base + (unsigned)j * 1024);
@@ -364,12 +350,12 @@ __global__ __launch_bounds__(kRedBlock) void reduce_ldsdma(const T* __restrict__
   for (int64_t k = issued; k < np; ++k) {
     const V16<T> v = ld16<NT>(reinterpret_cast<const V16<T>*>(src + k * step));
 #pragma unroll
-    for (int q = 0; q < N; ++q) acc[0] = red_combine<OP>(acc[0], red_map<OP>(to_f64<T>(v.v[q]), 0.0));
+    for (int q = 0; q < N; ++q) acc[0] = red_combine<OP>(acc[0], red_map<OP>(widen<T>(v.v[q]), 0.0));
   }
   // elements past the last whole piece: the grid's last block
   if (blockIdx.x == gridDim.x - 1)
     for (int64_t k = pieces * N * kWave + threadIdx.x; k < n; k += kRedBlock)
-      acc[0] = red_combine<OP>(acc[0], red_map<OP>(to_f64<T>(a[k]), 0.0));
+      acc[0] = red_combine<OP>(acc[0], red_map<OP>(widen<T>(a[k]), 0.0));
   double v = acc[0];
 #pragma unroll
   for (int g = 1; g < G; ++g) v = red_combine<OP>(v, acc[g]);
@@ -448,47 +434,35 @@ int launch_reduce(const void* a, const void* b, int64_t n, double* workspace, do
   static const bool chunked = getenv("BK_REDUCE_LAYOUT") && !strcmp(getenv("BK_REDUCE_LAYOUT"), "chunk");
   static const bool ldsdma = getenv("BK_REDUCE_LAYOUT") && !strcmp(getenv("BK_REDUCE_LAYOUT"), "ldsdma");
   static const bool ldsdma_s = getenv("BK_REDUCE_LAYOUT") && !strcmp(getenv("BK_REDUCE_LAYOUT"), "ldsdma_stride");
+  // lab: BK_REDUCE_UNROLL=4/8 -- fewer loads in flight per lane, for grids with more waves (nt arrays only)
+  static const int unroll = (int)env_int("BK_REDUCE_UNROLL", kRedUnroll);
   const bool nt = stream_nt(n * (int64_t)sizeof(T) * (kTwoOperands<OP> ? 2 : 1));
+  const T *pa = (const T*)a, *pb = (const T*)b;
   if constexpr (!kTwoOperands<OP>) {
-    if (ldsdma || ldsdma_s) {
-      if (ldsdma_s) {
-        if (nt) reduce_ldsdma<T, OP, true, true><<<g, kRedBlock, 0, s>>>((const T*)a, n, workspace, ticket, out);
-        else reduce_ldsdma<T, OP, false, true><<<g, kRedBlock, 0, s>>>((const T*)a, n, workspace, ticket, out);
-      } else if (nt) {
-        reduce_ldsdma<T, OP, true, false><<<g, kRedBlock, 0, s>>>((const T*)a, n, workspace, ticket, out);
+    if (ldsdma || ldsdma_s)
+      return dispatch_flag(ldsdma_s, [&](auto strided) {
+        return dispatch_flag(nt, [&](auto ntc) {
+          reduce_ldsdma<T, OP, decltype(ntc)::value, decltype(strided)::value>
+              <<<g, kRedBlock, 0, s>>>(pa, n, workspace, ticket, out);
+          return launch_status();
+        });
+      });
+  }
+  return dispatch_flag(chunked, [&](auto chunk) {
+    return dispatch_flag(nt, [&](auto ntc) {
+      constexpr bool NT = decltype(ntc)::value;
+      if constexpr (decltype(chunk)::value) {
+        reduce_chunked<T, OP, NT><<<g, kRedBlock, 0, s>>>(pa, pb, n, workspace, ticket, out);
+      } else if constexpr (NT) {
+        if (unroll == 4) reduce_1pass<T, OP, true, 4><<<g, kRedBlock, 0, s>>>(pa, pb, n, workspace, ticket, out);
+        else if (unroll == 8) reduce_1pass<T, OP, true, 8><<<g, kRedBlock, 0, s>>>(pa, pb, n, workspace, ticket, out);
+        else reduce_1pass<T, OP, true><<<g, kRedBlock, 0, s>>>(pa, pb, n, workspace, ticket, out);
       } else {
-        reduce_ldsdma<T, OP, false, false><<<g, kRedBlock, 0, s>>>((const T*)a, n, workspace, ticket, out);
+        reduce_1pass<T, OP, false><<<g, kRedBlock, 0, s>>>(pa, pb, n, workspace, ticket, out);
       }
       return launch_status();
-    }
-  }
-  if (chunked) {
-    if (nt) reduce_chunked<T, OP, true><<<g, kRedBlock, 0, s>>>((const T*)a, (const T*)b, n, workspace, ticket, out);
-    else reduce_chunked<T, OP, false><<<g, kRedBlock, 0, s>>>((const T*)a, (const T*)b, n, workspace, ticket, out);
-  } else if (nt) {
-    // lab: BK_REDUCE_UNROLL=4/8 -- fewer loads in flight per lane, for grids with more waves
-    static const int unroll = (int)env_int("BK_REDUCE_UNROLL", kRedUnroll);
-    if (unroll == 4)
-      reduce_1pass<T, OP, true, 4><<<g, kRedBlock, 0, s>>>((const T*)a, (const T*)b, n, workspace, ticket, out);
-    else if (unroll == 8)
-      reduce_1pass<T, OP, true, 8><<<g, kRedBlock, 0, s>>>((const T*)a, (const T*)b, n, workspace, ticket, out);
-    else
-      reduce_1pass<T, OP, true><<<g, kRedBlock, 0, s>>>((const T*)a, (const T*)b, n, workspace, ticket, out);
-  } else {
-    reduce_1pass<T, OP, false><<<g, kRedBlock, 0, s>>>((const T*)a, (const T*)b, n, workspace, ticket, out);
-  }
-  return launch_status();
-}
-
-// bk_reduce on a kBool mask: op 0 the count of non-zero bytes, 3 any, 4 all (mask.hip)
-int reduce_bool(int op, const void* a, int64_t n, void* workspace, void* out, hipStream_t stream);
-
-template <typename T, int... OPS>
-int dispatch_reduce(int op, const void* a, const void* b, int64_t n, double* ws, double* out, hipStream_t s,
-                    std::integer_sequence<int, OPS...>) {
-  int rc = kBadArgument;
-  ((op == OPS ? (rc = launch_reduce<T, OPS>(a, b, n, ws, out, s), 0) : 0), ...);
-  return rc;
+    });
+  });
 }
 
 // ---- axis reductions of a 2-D row-major matrix (numpy sum/mean(axis=)) -------
@@ -525,10 +499,10 @@ __global__ __launch_bounds__(256) void colsum_1pass(const T* __restrict__ x, int
     double a0 = 0.0, a1 = 0.0;
     int64_t r = r0;
     for (; r + 1 < r1; r += 2) {
-      a0 += to_f64<T>(x[r * ld + col]);
-      a1 += to_f64<T>(x[(r + 1) * ld + col]);
+      a0 += widen<T>(x[r * ld + col]);
+      a1 += widen<T>(x[(r + 1) * ld + col]);
     }
-    if (r < r1) a0 += to_f64<T>(x[r * ld + col]);
+    if (r < r1) a0 += widen<T>(x[r * ld + col]);
     publish(part + (int64_t)blockIdx.y * cols + col, a0 + a1);
   }
   if (!take_last_ticket(tickets + blockIdx.x, gridDim.y)) return;
@@ -546,8 +520,6 @@ __global__ __launch_bounds__(256) void colsum_1pass(const T* __restrict__ x, int
 // (completion ticket) folds the strip's chunk partials in chunk order.  Narrow
 // strips keep the chunk count low (4096^2: 32 strips x 32 chunks) -- the
 // 512-column version spent most of its 13.6-15.4 us folding 64 chunks.
-constexpr int kColWaves = 16;
-
 template <typename T, typename TO>
 __global__ __launch_bounds__(kColWaves * 64) void colsum_tile_v(const T* __restrict__ x, int64_t rows, int64_t cols,
                                                               int64_t ld, int64_t rows_per_chunk,
@@ -574,12 +546,12 @@ __global__ __launch_bounds__(kColWaves * 64) void colsum_tile_v(const T* __restr
 #pragma unroll
       for (int q = 0; q < 4; ++q)
 #pragma unroll
-        for (int j = 0; j < V; ++j) acc[j] += to_f64<T>(v[q].v[j]);
+        for (int j = 0; j < V; ++j) acc[j] += widen<T>(v[q].v[j]);
     }
     for (; r < r1; r += kStep) {
       const V16<T> v = *reinterpret_cast<const V16<T>*>(x + r * ld + col0);
 #pragma unroll
-      for (int j = 0; j < V; ++j) acc[j] += to_f64<T>(v.v[j]);
+      for (int j = 0; j < V; ++j) acc[j] += widen<T>(v.v[j]);
     }
   }
   // row lanes 0..3 of each column lane: (0 + 1) + (2 + 3), same in every lane
@@ -616,7 +588,7 @@ __global__ __launch_bounds__(256) void rowsum(const T* __restrict__ x, int64_t r
   const int lane = threadIdx.x & 63;
   const T* p = x + row * ld;
   double acc = 0.0;
-  for (int64_t c = lane; c < cols; c += 64) acc += to_f64<T>(p[c]);
+  for (int64_t c = lane; c < cols; c += 64) acc += widen<T>(p[c]);
   acc = wave_reduce<kRedSum>(acc);
   if (lane == 0) out[row] = (TO)(acc * scale);
 }
@@ -637,16 +609,16 @@ __global__ __launch_bounds__(256) void rowsum_v(const T* __restrict__ x, int64_t
     const V16<T> u = p[c], w = p[c + 64], y = p[c + 128], z = p[c + 192];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      a0 += to_f64<T>(u.v[j]);
-      a1 += to_f64<T>(w.v[j]);
-      a2 += to_f64<T>(y.v[j]);
-      a3 += to_f64<T>(z.v[j]);
+      a0 += widen<T>(u.v[j]);
+      a1 += widen<T>(w.v[j]);
+      a2 += widen<T>(y.v[j]);
+      a3 += widen<T>(z.v[j]);
     }
   }
   for (; c < nv; c += 64) {
     const V16<T> u = p[c];
 #pragma unroll
-    for (int j = 0; j < V; ++j) a0 += to_f64<T>(u.v[j]);
+    for (int j = 0; j < V; ++j) a0 += widen<T>(u.v[j]);
   }
   const double acc = wave_reduce<kRedSum>((a0 + a1) + (a2 + a3));
   if (lane == 0) out[row] = (TO)(acc * scale);
@@ -724,30 +696,27 @@ BK_API int bk_rand_reduce(int op, int dtype, int64_t n, uint64_t seed, uint64_t 
   double* ws = (double*)workspace;
   unsigned* t = reinterpret_cast<unsigned*>(ws + kRedMaxBlocks);
   double* o = (double*)out;
-  if (dtype == kF64) {
-    if (op == kRedSum) rand_reduce_f64<kRedSum><<<g, kRedBlock, 0, stream>>>(n, k0, k1, offset, lo, hi - lo, ws, t, o);
-    else rand_reduce_f64<kRedSquareSum><<<g, kRedBlock, 0, stream>>>(n, k0, k1, offset, lo, hi - lo, ws, t, o);
-  } else {
-    if (op == kRedSum)
-      rand_reduce_f32<kRedSum><<<g, kRedBlock, 0, stream>>>(n, k0, k1, offset, (float)lo, (float)(hi - lo), ws, t, o);
-    else
-      rand_reduce_f32<kRedSquareSum><<<g, kRedBlock, 0, stream>>>(n, k0, k1, offset, (float)lo, (float)(hi - lo), ws, t,
-                                                                  o);
-  }
-  return launch_status();
+  return dispatch_flag(dtype == kF64, [&](auto f64) {
+    return dispatch_flag(op == kRedSum, [&](auto sum) {
+      constexpr int OP = decltype(sum)::value ? kRedSum : kRedSquareSum;
+      if constexpr (decltype(f64)::value)
+        rand_reduce_f64<OP><<<g, kRedBlock, 0, stream>>>(n, k0, k1, offset, lo, hi - lo, ws, t, o);
+      else
+        rand_reduce_f32<OP><<<g, kRedBlock, 0, stream>>>(n, k0, k1, offset, (float)lo, (float)(hi - lo), ws, t, o);
+      return launch_status();
+    });
+  });
 }
 
 BK_API int bk_reduce(int op, int dtype, const void* a, const void* b, int64_t n, void* workspace, void* out,
                      hipStream_t stream) {
   if (!a || !out || !workspace || n < 0 || op < 0 || op >= kRedCount || ((op == kRedDot || op == kRedMaxAbsDiff) && !b)) return kBadArgument;
-  using Ops = std::make_integer_sequence<int, kRedCount>;
-  switch (dtype) {
-    case kF64: return dispatch_reduce<double>(op, a, b, n, (double*)workspace, (double*)out, stream, Ops{});
-    case kF32: return dispatch_reduce<float>(op, a, b, n, (double*)workspace, (double*)out, stream, Ops{});
-    case kBF16: return dispatch_reduce<uint16_t>(op, a, b, n, (double*)workspace, (double*)out, stream, Ops{});
-    case kBool: return reduce_bool(op, a, n, workspace, out, stream);  // count / any / all (mask.hip)
-  }
-  return kBadArgument;
+  if (dtype == kBool) return reduce_bool(op, a, n, workspace, out, stream);  // count / any / all (mask.hip)
+  return dispatch_dtype<double, float, uint16_t>(dtype, [&](auto t) {
+    return dispatch_op<kRedCount>(op, [&](auto opc) {
+      return launch_reduce<typename decltype(t)::type, decltype(opc)::value>(a, b, n, (double*)workspace, (double*)out, stream);
+    });
+  });
 }
 
 BK_API int bk_reduce_axis(int op, int dtype, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis, void* out,

@@ -33,11 +33,6 @@ constexpr int kDigits = 1 << kDigitBits;
 
 constexpr int kMaxBins = BK_MAX_BINS;
 
-template <typename T> struct alignas(16) V16 {
-  static constexpr int N = 16 / sizeof(T);
-  T v[N];
-};
-
 // hist[idx] += 1 for every lane with `on` set; idx is in bounds for those lanes
 __device__ __forceinline__ void lds_count(unsigned* hist, unsigned idx, bool on) {
   const int lane = threadIdx.x & (kWave - 1);
@@ -300,13 +295,13 @@ template <typename K>
 int launch_select(const void* x, int64_t n, const Ranks& ranks, int nranks, double* out, SelectWs* ws, hipStream_t q) {
   const unsigned g = grid_for<K>(n);
   const int64_t head = head_elements<K>(x, n);
-  const bool nt = stream_nt(n * (int64_t)sizeof(K));
-  for (int pass = 0; pass < (int)sizeof(K); ++pass) {
-    if (nt) select_pass<K, true><<<g, kBlock, 0, q>>>((const K*)x, n, head, pass, nranks, ranks, ws, out);
-    else select_pass<K, false><<<g, kBlock, 0, q>>>((const K*)x, n, head, pass, nranks, ranks, ws, out);
-    if (hipGetLastError() != hipSuccess) return kLaunchFailed;
-  }
-  return kOk;
+  return dispatch_flag(stream_nt(n * (int64_t)sizeof(K)), [&](auto nt) {
+    for (int pass = 0; pass < (int)sizeof(K); ++pass) {
+      select_pass<K, decltype(nt)::value><<<g, kBlock, 0, q>>>((const K*)x, n, head, pass, nranks, ranks, ws, out);
+      if (launch_status() != kOk) return (int)kLaunchFailed;
+    }
+    return (int)kOk;
+  });
 }
 
 // ---- histogram ----------------------------------------------------------------------
@@ -319,10 +314,6 @@ struct HistWs {
   unsigned long long table[kMaxBins];  // merged counts; zero between launches
   alignas(256) unsigned ticket[64];
 };
-
-__device__ __forceinline__ double widen(uint64_t b) { return bits_to_double(b); }
-__device__ __forceinline__ double widen(uint32_t b) { return bits_to_double(b); }
-__device__ __forceinline__ double widen(uint16_t b) { return bits_to_double(b); }
 
 template <typename K, bool NT>
 __global__ __launch_bounds__(kBlock) void histogram_kernel(const K* __restrict__ x, int64_t n, int64_t head,
@@ -340,7 +331,7 @@ __global__ __launch_bounds__(kBlock) void histogram_kernel(const K* __restrict__
   const double scale = width > 0.0 ? (double)bins / width : 0.0;  // (inf width: 0, the search decides)
 
   for_each_element<K, NT>(x, n, head, [&](K u) {
-    const double v = widen(u);
+    const double v = bits_to_double(u);
     const bool in = v >= e0 && v <= elast;  // NaN: false
     int b = 0;
     if (in) {
@@ -392,11 +383,10 @@ int launch_histogram(const void* x, int64_t n, const double* edges, int bins, un
   const unsigned g = grid_for<K>(n);
   const int64_t head = head_elements<K>(x, n);
   const size_t lds = (size_t)(bins + 1) * sizeof(double) + (size_t)bins * sizeof(unsigned);
-  if (stream_nt(n * (int64_t)sizeof(K)))
-    histogram_kernel<K, true><<<g, kBlock, lds, q>>>((const K*)x, n, head, edges, bins, ws, counts);
-  else
-    histogram_kernel<K, false><<<g, kBlock, lds, q>>>((const K*)x, n, head, edges, bins, ws, counts);
-  return launch_status();
+  return dispatch_flag(stream_nt(n * (int64_t)sizeof(K)), [&](auto nt) {
+    histogram_kernel<K, decltype(nt)::value><<<g, kBlock, lds, q>>>((const K*)x, n, head, edges, bins, ws, counts);
+    return launch_status();
+  });
 }
 
 }  // namespace stats

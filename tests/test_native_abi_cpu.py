@@ -8,7 +8,10 @@ without loading the library into Python:
 * the size of every ticketed workspace against the numbers of the per-kernel
   exports that bk_workspace_bytes replaced -- a workspace smaller than its
   kernel expects would be an out-of-bounds write on the GPU -- through a small
-  program of its own (tests/native_abi_main.cpp) linked against the library."""
+  program of its own (tests/native_abi_main.cpp) linked against the library.
+
+And the launch dispatch the kernel files share (csrc/kernels/bk_dispatch.hpp), through a
+program of its own (tests/dispatch_main.cpp) built by g++ with sanitizers."""
 
 import ctypes
 import os
@@ -137,3 +140,14 @@ def test_workspace_sizes_are_the_replaced_exports(library, tmp_path):
     # unknown kinds and a null workspace: kBadArgument (1), answered before any HIP call
     assert [p for p in lines if p[0].startswith("init")] == [["init", "-1", "1"], ["init", str(len(WORKSPACE_BYTES)), "1"],
                                                              ["init_null", "1"]]
+
+
+def test_launch_dispatch_reaches_one_instantiation(tmp_path):
+    """csrc/kernels/bk_dispatch.hpp alone, as plain C++ under ASan / UBSan (tests/dispatch_main.cpp checks
+    each call itself): an op, flag or dtype code reaches its one instantiation, any other is kBadArgument."""
+    prog = str(tmp_path / "dispatch_main")
+    subprocess.run([_build.CXX, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-static-libasan", os.path.join(ROOT, "tests", "dispatch_main.cpp"), "-o", prog],
+                   check=True, capture_output=True, text=True)
+    run = subprocess.run([prog], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stdout == "dispatch ok\n", run.stdout + run.stderr
