@@ -66,10 +66,9 @@ class HipDevice final : public broker::Device {
   // straight into pinned host-coherent memory, so a reduce costs one stream
   // sync instead of a staging copy plus the sync.
   struct Ctx {
-    hipStream_t s = nullptr;   // the stream the session's latest op went to (waits and frees follow it)
-    hipStream_t lo = nullptr;  // normal priority: GEMMs, large draws and passes
-    hipStream_t hi = nullptr;  // high priority: the short dependent ops (reductions, casts, GEMV), or null
-    hipEvent_t hop = nullptr;  // orders the two streams when an op moves from one to the other
+    hipStream_t s = nullptr;   // the lane the session is on: lo or hi (launches, waits and frees all go here)
+    hipStream_t lo = nullptr;  // normal priority
+    hipStream_t hi = nullptr;  // high priority: batches of short dependent ops only (set_lane), or null
     // the kernels' scratch workspaces by kind: the reductions' from the
     // start, the others allocated on first use (workspace())
     void* ws[BK_WS_COUNT] = {};
@@ -345,17 +344,14 @@ class HipDevice final : public broker::Device {
     hipSetDevice(0);
     hipStreamCreateWithFlags(&c->lo, hipStreamNonBlocking);
     c->s = c->lo;
-    if (prio_) {
-      int least = 0, greatest = 0;
-      if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least &&
-          hipStreamCreateWithPriority(&c->hi, hipStreamNonBlocking, greatest) == hipSuccess &&
-          hipEventCreateWithFlags(&c->hop, hipEventDisableTiming) == hipSuccess) {
-      } else {
-        if (c->hi) hipStreamDestroy(c->hi);
-        c->hi = nullptr;
-      }
-    }
-    workspace(c, BK_WS_REDUCE);  // (initialised on c->s: ordered before every reduction on this stream)
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || greatest == least ||
+        hipStreamCreateWithPriority(&c->hi, hipStreamNonBlocking, greatest) != hipSuccess)
+      c->hi = nullptr;  // (no priority range: one lane)
+    workspace(c, BK_WS_REDUCE);
+    // the workspace is initialised on lo, and the session's first batch may
+    // run on hi: finished now, once per context
+    hipStreamSynchronize(c->lo);
     bk.malloc(&c->scalar, 256);
     void* page = nullptr;
     if (hipHostMalloc(&page, 64, hipHostMallocCoherent) == hipSuccess) c->slot = (double*)page;
@@ -370,6 +366,7 @@ class HipDevice final : public broker::Device {
     Ctx* c = (Ctx*)p;
     reap(c, true);  // the session drained the stream before handing it back
     if (c->seg_open) wait(c);  // (launches after its last wait: close that segment)
+    c->s = c->lo;              // every session starts on the normal lane
     std::lock_guard<std::mutex> lk(mu_);
     pool_.push_back(c);
   }
@@ -396,11 +393,24 @@ class HipDevice final : public broker::Device {
     c->pending.emplace_back(ev, p);
   }
   static hipStream_t st(void* p) { return ((Ctx*)p)->s; }
+  // The session changes lane only while it is drained (broker_core.hpp
+  // Session::plan): nothing of it is queued or running on either stream, so
+  // the host wait that drained it is all the ordering the two streams need --
+  // no event, no hipStreamWaitEvent.  Whatever follows c->s (the waits, the
+  // deferred frees of release(), a workspace's initialisation, the GPU-timing
+  // segments) therefore stays correct across a change: the stream it leaves
+  // is empty.  The per-op version of this (BEE_BROKER_PRIO=1, each short op
+  // hopping to the priority stream behind an event) lost 2% RPS to its hops
+  // (profiles/archive/r4_served_prio_ab.md).
+  void set_lane(void* p, bool priority) override {
+    Ctx* c = (Ctx*)p;
+    c->s = priority && c->hi ? c->hi : c->lo;
+  }
 
   // The session's workspace of `kind` (enum BkWorkspace), allocated and
   // initialised on first use; null if the allocation fails.  The init is
-  // queued on c->s, the session's latest stream: pick() orders a later hop to
-  // the other stream after it.
+  // queued on c->s, ahead of the launch that asked for it; the session leaves
+  // that stream only once it is drained (set_lane).
   void* workspace(Ctx* c, int kind) {
     void*& ws = c->ws[kind];
     if (!ws) {
@@ -409,31 +419,6 @@ class HipDevice final : public broker::Device {
     }
     return ws;
   }
-
-  // The stream for the session's next op.  Short ops -- reductions, casts,
-  // small passes, GEMV-sized products -- go to the high-priority stream, so
-  // the command processor dispatches them ahead of other sessions' queued
-  // GEMMs and large passes (under 8 concurrent sandboxes a 6 us row sum
-  // averaged 37 us and a 2.4 us reduction 19 us behind them,
-  // profiles/archive/r3_final_served_kernels.csv).  One session's ops stay in issue
-  // order: moving to the other stream records an event on the one it leaves
-  // and makes the new one wait for it (GPU-side), and waits / deferred frees
-  // follow the latest stream (which by this chain follows everything before).
-  hipStream_t pick(void* p, bool short_op) {
-    Ctx* c = (Ctx*)p;
-    hipStream_t want = short_op && c->hi ? c->hi : c->lo;
-    if (want != c->s) {
-      if (hipEventRecord(c->hop, c->s) != hipSuccess || hipStreamWaitEvent(want, c->hop, 0) != hipSuccess) {
-        hipStreamSynchronize(c->s);  // (ordering by a host wait if the event path fails)
-      }
-      c->s = want;
-    }
-    return want;
-  }
-  // what counts as short: under ~16 MiB of memory traffic or ~2^31 flops
-  static constexpr int64_t kShortBytes = 16ll << 20;
-  static bool short_bytes(int64_t n, int64_t elem, int operands = 1) { return n * elem * operands <= kShortBytes; }
-  static int64_t elem_bytes(uint32_t dt) { return dt == 1 ? 8 : dt == 2 ? 2 : 4; }
 
   int malloc(void** p, uint64_t n) override { return bk.malloc(p, (int64_t)n); }
   void free(void* p) override { bk.free(p); }
@@ -452,30 +437,30 @@ class HipDevice final : public broker::Device {
   bool sync(void* s) override { return wait((Ctx*)s); }
   int rand(uint32_t kind, void* y, int64_t n, uint32_t dt, uint64_t seed, uint64_t off, double a, double b,
            void* s) override {
-    return timed(s, pick(s, short_bytes(n, elem_bytes(dt))), [&](hipStream_t q) {
+    return timed(s, st(s), [&](hipStream_t q) {
       return kind == 0 ? bk.rand_uniform(y, n, (int)dt, seed, off, a, b, q) : bk.rand_normal(y, n, (int)dt, seed, off, a, b, q);
     });
   }
   int rand_dist(uint32_t kind, void* y, int64_t n, uint32_t dt, uint64_t seed, uint64_t off, double p0, double p1,
                 void* s) override {
-    return timed(s, pick(s, short_bytes(n, elem_bytes(dt))),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.rand_dist((int)kind, y, n, (int)dt, seed, off, p0, p1, q); });
   }
   int unary(uint32_t op, uint32_t dt, const void* x, void* y, int64_t n, void* s) override {
-    return timed(s, pick(s, short_bytes(n, elem_bytes(dt), 2)),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.unary((int)op, (int)dt, x, y, n, q); });
   }
   int binary(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double sc, void* y, int64_t n,
              void* s) override {
-    return timed(s, pick(s, short_bytes(n, elem_bytes(dt), 3)),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.binary((int)op, (int)dt, (int)mode, a, b, sc, y, n, q); });
   }
   int cast(uint32_t sdt, uint32_t ddt, const void* x, void* y, int64_t n, void* s) override {
-    return timed(s, pick(s, short_bytes(n, elem_bytes(sdt) + elem_bytes(ddt))),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.cast((int)sdt, (int)ddt, x, y, n, q); });
   }
   int fill(void* y, int64_t nbytes, uint64_t pattern, uint32_t width, void* s) override {
-    return timed(s, pick(s, nbytes <= kShortBytes), [&](hipStream_t q) { return bk.fill(y, nbytes, pattern, (int)width, q); });
+    return timed(s, st(s), [&](hipStream_t q) { return bk.fill(y, nbytes, pattern, (int)width, q); });
   }
   int fetch(Ctx* c, int rc, double* out) {
     if (rc != 0) return rc;
@@ -490,7 +475,7 @@ class HipDevice final : public broker::Device {
   }
   int reduce(uint32_t op, uint32_t dt, const void* a, const void* b, int64_t n, double* out, void* s) override {
     Ctx* c = (Ctx*)s;
-    const int rc = timed(s, pick(s, short_bytes(n, elem_bytes(dt), b ? 2 : 1)), [&](hipStream_t q) {
+    const int rc = timed(s, st(s), [&](hipStream_t q) {
       return bk.reduce((int)op, (int)dt, a, b, n, c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
     });
     return fetch(c, rc, out);
@@ -498,35 +483,34 @@ class HipDevice final : public broker::Device {
   int rand_reduce(uint32_t op, uint32_t dt, int64_t n, uint64_t seed, uint64_t off, double lo, double hi, double* out,
                   void* s) override {
     Ctx* c = (Ctx*)s;
-    // (compute-bound: ~4 us per 4M values)
-    const int rc = timed(s, pick(s, n <= (1ll << 22)), [&](hipStream_t q) {
+    const int rc = timed(s, st(s), [&](hipStream_t q) {
       return bk.rand_reduce((int)op, (int)dt, n, seed, off, lo, hi, c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
     });
     return fetch(c, rc, out);
   }
   int gemm(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc, float alpha,
            float beta, int odt, void* s) override {
-    return timed(s, pick(s, short_gemm(M, N, K)),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.gemm_bf16_tn(A, Bt, C, M, N, K, lda, ldb, ldc, alpha, beta, odt, q); });
   }
   int gemm_nn(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, float alpha,
               float beta, int odt, void* s) override {
-    return timed(s, pick(s, short_gemm(M, N, K)),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.gemm_bf16_nn(A, B, C, M, N, K, lda, ldb, ldc, alpha, beta, odt, q); });
   }
   int gemm_fp(uint32_t dt, bool ta, bool tb, const void* A, const void* B, void* C, int M, int N, int K, int64_t lda,
               int64_t ldb, int64_t ldc, void* s) override {
-    return timed(s, pick(s, short_gemm(M, N, K)),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.gemm_fp((int)dt, ta, tb, A, B, C, M, N, K, lda, ldb, ldc, q); });
   }
   int gemm_f32x6(bool ta, bool tb, const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb,
                  int64_t ldc, void* ws, uint64_t ws_bytes, void* s) override {
-    return timed(s, pick(s, short_gemm(M, N, K)), [&](hipStream_t q) {
+    return timed(s, st(s), [&](hipStream_t q) {
       return bk.gemm_f32x6(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, ws, (int64_t)ws_bytes, q);
     });
   }
   int transpose(int sdt, int ddt, const void* in, void* out, int rows, int cols, int ldi, int ldo, void* s) override {
-    return timed(s, pick(s, short_bytes((int64_t)rows * cols, elem_bytes(sdt) + elem_bytes(ddt))),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.transpose(sdt, ddt, in, out, rows, cols, ldi, ldo, q); });
   }
   int reduce_axis(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,
@@ -535,12 +519,12 @@ class HipDevice final : public broker::Device {
     if (!ws) return broker::kOutOfMemory;
     // a row / column sum reads the matrix once: ~64 MiB at 4096^2 f32 is
     // ~10 us -- short next to the GEMM that produced it
-    return timed(s, pick(s, short_bytes(rows * ld, elem_bytes(dt)) || rows * ld <= (16ll << 20)),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.reduce_axis((int)op, (int)dt, x, rows, cols, ld, (int)axis, y, ws, q); });
   }
   int broadcast(uint32_t op, uint32_t dt, uint32_t kind, bool swapped, const void* a, const void* v, void* y,
                 int64_t rows, int64_t cols, int64_t lda, int64_t ldy, void* s) override {
-    return timed(s, pick(s, short_bytes(rows * cols, elem_bytes(dt), 2)), [&](hipStream_t q) {
+    return timed(s, st(s), [&](hipStream_t q) {
       return bk.broadcast((int)op, (int)dt, (int)kind, swapped ? 1 : 0, a, rows, cols, lda, v, y, ldy, q);
     });
   }
@@ -549,38 +533,37 @@ class HipDevice final : public broker::Device {
     void* ws = workspace((Ctx*)s, BK_WS_AXIS_STAT);
     if (!ws) return broker::kOutOfMemory;
     // (the variance reads the matrix twice)
-    return timed(s, pick(s, short_bytes(rows * cols, elem_bytes(dt), op >= 2 ? 2 : 1)), [&](hipStream_t q) {
+    return timed(s, st(s), [&](hipStream_t q) {
       return bk.axis_stat((int)op, (int)dt, x, rows, cols, ld, (int)axis, divisor, y, ws, q);
     });
   }
   // boolean masks: a mask is one byte per element
   int compare(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double sc, void* y, int64_t n,
               void* s) override {
-    return timed(s, pick(s, short_bytes(n, elem_bytes(dt) * (mode == 0 ? 2 : 1) + 1)),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.compare((int)op, (int)dt, (int)mode, a, b, sc, y, n, q); });
   }
   int compare_count(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double sc, int64_t n,
                     double* out, void* s) override {
     Ctx* c = (Ctx*)s;
-    const int rc = timed(s, pick(s, short_bytes(n, elem_bytes(dt), mode == 0 ? 2 : 1)), [&](hipStream_t q) {
+    const int rc = timed(s, st(s), [&](hipStream_t q) {
       return bk.compare_count((int)op, (int)dt, (int)mode, a, b, sc, n, c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
     });
     return fetch(c, rc, out);
   }
   int mask_logical(uint32_t op, const void* a, const void* b, void* y, int64_t n, void* s) override {
-    return timed(s, pick(s, short_bytes(n, 1, 3)),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.mask_logical((int)op, a, b, y, n, q); });
   }
   int where(uint32_t dt, const void* m, uint32_t flags, const void* a, const void* b, double sa, double sb, void* y,
             int64_t n, void* s) override {
-    return timed(s, pick(s, short_bytes(n, elem_bytes(dt) * 3 + 1)),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.where((int)dt, m, (int)flags, a, b, sa, sb, y, n, q); });
   }
   int compress(uint32_t dt, const void* x, const void* m, int64_t n, void* y, int64_t cap, void* s) override {
     void* ws = workspace((Ctx*)s, BK_WS_COMPRESS);
     if (!ws) return broker::kOutOfMemory;
-    const int64_t es = dt == broker::kDtBool ? 1 : elem_bytes(dt);
-    return timed(s, pick(s, short_bytes(n, 2 * es + 2)),
+    return timed(s, st(s),
                  [&](hipStream_t q) { return bk.compress((int)dt, x, m, n, y, cap, ws, q); });
   }
   // order statistics and histograms: results, edges and counts pass through
@@ -596,7 +579,7 @@ class HipDevice final : public broker::Device {
     void* ws = workspace(c, BK_WS_SELECT);
     if (!ws) return broker::kOutOfMemory;
     // one read of x per byte of the dtype
-    const int rc = timed(s, pick(s, short_bytes(n, elem_bytes(dt), (int)elem_bytes(dt))), [&](hipStream_t q) {
+    const int rc = timed(s, st(s), [&](hipStream_t q) {
       return bk.select((int)dt, x, n, ranks, (int)nranks, c->stats, ws, q);
     });
     if (rc != 0) return rc;
@@ -610,7 +593,7 @@ class HipDevice final : public broker::Device {
     if (!stats_scratch(c)) return broker::kOutOfMemory;
     void* ws = workspace(c, BK_WS_HISTOGRAM);
     if (!ws) return broker::kOutOfMemory;
-    hipStream_t q0 = pick(s, short_bytes(n, elem_bytes(dt)));
+    hipStream_t q0 = st(s);
     // (the caller's edges stay put until the wait below, or the one on the failure path)
     if (hipMemcpyAsync(c->stats + kStatsEdgesAt, edges, ((size_t)bins + 1) * 8, hipMemcpyHostToDevice, q0) != hipSuccess)
       return broker::kLaunchFailed;
@@ -640,16 +623,6 @@ class HipDevice final : public broker::Device {
 
  private:
   bool spin_wait_ = getenv("BEE_BROKER_WAIT") && !strcmp(getenv("BEE_BROKER_WAIT"), "spin");
-  // BEE_BROKER_PRIO=1: short ops on a high-priority stream (pick()).  Off by
-  // default: measured on MI355X (300 served headline Executes, 8 concurrent,
-  // profiles/archive/r4_served_prio_ab.md) the high-priority queue let reductions
-  // start beside other sessions' GEMMs instead of after them, where they ran
-  // slower and slowed the GEMMs: bk.reduce 181 vs 126 us and bk.rand_reduce
-  // 525 vs 423 us per op, rowsum 39 vs 32 us per kernel, 2763-2835 vs
-  // 2815-2880 RPS, +0.15 ms daemon CPU per Execute (the stream hops).
-  bool prio_ = getenv("BEE_BROKER_PRIO") && !strcmp(getenv("BEE_BROKER_PRIO"), "1");
-  // a GEMM whose work is a GEMV or a small product (<= 2^31 flops, ~2 us)
-  static bool short_gemm(int M, int N, int K) { return 2.0 * M * N * K <= 2147483648.0; }
   // default: relative backoff (2 us, then 1/8 of the wait so far): A/B on
   // MI355X, 4 interleaved runs each, broker CPU 0.30-0.33 vs 0.34-0.35 ms per
   // Execute, RPS 2500-2665 vs 2466-2550 (profiles/archive/r2_s3_broker_poll_ab.log).
@@ -817,9 +790,17 @@ void KernelBroker::serve(int fd, pid_t peer_pid) {
     broker::Session session(*dev_, std::move(peer), &live_bytes_);
     std::vector<char> payload, reply;
     broker::FrameReader frames(fd);
+    std::vector<broker::FrameView> batch;
+    size_t planned = 0;  // frames of the batch the session has seen that are still to be handled
     while (!stopping_) {
       uint32_t hdr[4];
+      if (planned == 0 && frames.batch(&batch)) {
+        CpuScope cpu(kCpuBroker);
+        session.plan(batch);
+        planned = batch.size();
+      }
       if (!frames.next(hdr, &payload)) break;
+      if (planned) planned--;
       const uint64_t len = payload.size();
       CpuScope cpu(kCpuBroker);
       RoctxRange range(broker::op_name(hdr[0]));

@@ -106,6 +106,24 @@ constexpr int kMaxConnsPerSandbox = 32;            // each one holds a broker th
 const char* op_name(uint32_t op);
 int dtype_size(uint32_t dt);  // 0 for unknown codes
 
+// What a frame puts on the session's stream, read from its payload alone
+// (nothing is looked up or validated: a frame the dispatch would refuse may
+// come out as anything).  Short: under ~16 MiB of memory traffic or ~2^31
+// flops -- reductions, casts, small passes, GEMV-sized products, microseconds
+// each; long: the GEMMs, large draws and passes.  kNoLaunch: bookkeeping only
+// (allocations, frees, queries, a bare wait).
+enum Weight { kNoLaunch = 0, kShort, kLong };
+constexpr int64_t kShortBytes = 16ll << 20;
+constexpr int64_t kShortLazyDraw = 1ll << 22;  // rand_reduce is compute-bound: ~4 us per 4M values
+// n elements of `elem` bytes over `operands` arrays stay within kShortBytes (no wrap)
+inline bool short_bytes(int64_t n, int64_t elem, int64_t operands = 1) {
+  int64_t b;
+  return n >= 0 && !__builtin_mul_overflow(n, elem, &b) && !__builtin_mul_overflow(b, operands, &b) && b <= kShortBytes;
+}
+// a GEMM whose work is a GEMV or a small product (<= 2^31 flops, ~2 us)
+inline bool short_gemm(int M, int N, int K) { return 2.0 * M * N * K <= 2147483648.0; }
+Weight frame_weight(uint32_t op, const char* payload, uint64_t len);
+
 // overflow-checked arithmetic for every size the broker derives from a frame
 inline bool mul_ok(uint64_t a, uint64_t b, uint64_t* out) { return !__builtin_mul_overflow(a, b, out); }
 inline bool add_ok(uint64_t a, uint64_t b, uint64_t* out) { return !__builtin_add_overflow(a, b, out); }
@@ -155,6 +173,10 @@ class Device {
   virtual int reduce(uint32_t op, uint32_t dt, const void* a, const void* b, int64_t n, double* out, void* s) = 0;
   virtual int rand_reduce(uint32_t op, uint32_t dt, int64_t n, uint64_t seed, uint64_t off, double lo, double hi,
                           double* out, void* s) = 0;
+  // the session's next launches go to its priority lane (or back to the
+  // normal one).  Only called while the session is drained: nothing of it is
+  // queued or running on either lane, so no event has to order them
+  virtual void set_lane(void* /*s*/, bool /*priority*/) {}
   virtual int gemm(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc, float alpha,
                    float beta, int odt, void* s) = 0;
   // C = A . B with B stored [K][N]; kBadArgument where the device has no such
@@ -244,12 +266,26 @@ struct Peer {
 // Frames of one connection, read through a 64 KB buffer: a client that
 // queues its fire-and-forget launches (ops/driver.py BrokerDriver._post)
 // delivers a batch in one send, and this takes it in one read
+// a frame still in the reader's buffer (valid until the reader reads again)
+struct FrameView {
+  uint32_t op, flags;
+  const char* payload;
+  uint64_t len;
+};
+
 class FrameReader {
  public:
   explicit FrameReader(int fd, uint64_t max_frame = kMaxFrame) : fd_(fd), max_(max_frame), buf_(64 << 10) {}
   // the next frame's header and payload; false on EOF, error or a frame
   // longer than max_frame (*too_large set)
   bool next(uint32_t hdr[4], std::vector<char>* payload, bool* too_large = nullptr);
+  // The batch that next() is about to deliver: the frames already buffered,
+  // up to and including the first one that wants a reply.  With an empty
+  // buffer it first does the one read() that next() would do (and blocks
+  // like it); it never reads otherwise.  False when there is no such batch:
+  // the closing frame is not wholly buffered, or a frame before it is longer
+  // than max_frame.  next() then delivers every frame as it would have.
+  bool batch(std::vector<FrameView>* out);
   static uint64_t reads() { return reads_.load(std::memory_order_relaxed); }  // read() calls, all readers
 
  private:
@@ -259,6 +295,9 @@ class FrameReader {
   uint64_t max_;
   std::vector<char> buf_;
   size_t beg_ = 0, end_ = 0;
+  // bytes have arrived since the last walk that found no batch (a walk from
+  // further on in the same bytes finds none either)
+  bool fresh_ = true;
 };
 
 // response header and payload in one write when it is small (one read takes
@@ -276,6 +315,22 @@ class Session {
   // fire-and-forget requests (their first failure is reported by the next
   // request that wants a reply).  Returns the status sent (or deferred).
   int32_t handle(uint32_t op, uint32_t flags, const char* payload, uint64_t len, std::vector<char>* reply, bool* send);
+
+  // Look at a whole batch (FrameReader::batch) before its frames are handled,
+  // one by one and in order, by handle(): it decides the lane the batch runs
+  // on.  The session is drained when it has launched nothing since its
+  // last completed wait for everything it had launched.  A batch that starts
+  // drained runs on the priority lane if every launching frame of it is
+  // short (frame_weight), else on the normal lane: a sandbox's dependent
+  // handful of small kernels then overtakes other sessions' queued GEMMs and
+  // large draws instead of standing in line behind them.  A batch that starts
+  // undrained stays where the session is, and so does every frame outside a
+  // batch; so the lane only changes while the other one is empty, the host
+  // wait that drained the session is what orders the two, and everything that
+  // follows the device's current stream (deferred frees, workspace
+  // initialisation, the GPU-timing segments) stays correct with no event
+  // between them.  BEE_BROKER_LANES=0: always the normal lane.
+  void plan(const std::vector<FrameView>& batch);
 
   int64_t charged() const { return conn_bytes_; }
   size_t buffers() const { return bufs_.size(); }
@@ -305,6 +360,9 @@ class Session {
   // outputs the op being dispatched overwrites entirely: marked clean only
   // if it succeeds (node-based map: the pointers survive the dispatch)
   std::vector<Buf*> pending_clean_;
+  bool drained_ = true;    // nothing launched since the last completed wait for all launches
+  bool waited_ = false;    // the op being dispatched completed such a wait
+  bool lane_ = false;      // on the priority lane
 };
 
 }  // namespace broker

@@ -72,6 +72,7 @@ class HostDevice final : public Device {
   }
   bool sync(void*) override { return true; }
   int rand(uint32_t, void* y, int64_t n, uint32_t dt, uint64_t seed, uint64_t, double, double, void*) override {
+    note("rand");
     if (n < 0) return kBadArgument;
     touch_w(y, (uint64_t)n * dtype_size(dt), (uint8_t)seed);
     return 0;
@@ -94,6 +95,7 @@ class HostDevice final : public Device {
   // 53-bit / 24-bit uniforms of the dist streams -- so a read-back is checked
   int rand_dist(uint32_t kind, void* y, int64_t n, uint32_t dt, uint64_t seed, uint64_t off, double p0, double p1,
                 void*) override {
+    note("rand_dist");
     if (kind >= kDistCount || dt > 1 || n < 0 || !dist_params_ok(kind, p0, p1)) return kBadArgument;
     if (kind != 0) {
       touch_w(y, (uint64_t)n * dtype_size(dt), (uint8_t)kind);
@@ -118,12 +120,14 @@ class HostDevice final : public Device {
     return 0;
   }
   int unary(uint32_t op, uint32_t dt, const void* x, void* y, int64_t n, void*) override {
+    note("unary");
     if (op > 31 || dt > 2) return kBadArgument;
     copy(y, x, (uint64_t)n * dtype_size(dt));
     return 0;
   }
   int binary(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double, void* y, int64_t n,
              void*) override {
+    note("binary");
     if (op > 31 || dt > 2 || mode > 2 || (mode == 0 && !b)) return kBadArgument;
     const uint64_t nb = (uint64_t)n * dtype_size(dt);
     if (b) sum(b, nb);
@@ -131,16 +135,19 @@ class HostDevice final : public Device {
     return 0;
   }
   int cast(uint32_t s, uint32_t d, const void* x, void* y, int64_t n, void*) override {
+    note("cast");
     if (s > 2 || d > 2 || s == d) return kBadArgument;
     sum(x, (uint64_t)n * dtype_size(s));
     touch_w(y, (uint64_t)n * dtype_size(d), 1);
     return 0;
   }
   int fill(void* y, int64_t nbytes, uint64_t pattern, uint32_t, void*) override {
+    note("fill");
     touch_w(y, (uint64_t)nbytes, (uint8_t)pattern);
     return 0;
   }
   int reduce(uint32_t op, uint32_t dt, const void* a, const void* b, int64_t n, double* out, void*) override {
+    note("reduce");
     if (dt == kDtBool) {  // a mask of n bytes: count, any, all
       if (op != 0 && op != 3 && op != 4) return kBadArgument;
       *out = sum(a, (uint64_t)n);
@@ -154,6 +161,7 @@ class HostDevice final : public Device {
   // cap * size of a compress output
   int compare(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double, void* y, int64_t n,
               void*) override {
+    note("compare");
     if (op > 5 || dt > 2 || mode > 1 || (mode == 0 && !b)) return kBadArgument;
     const double v = sum(a, (uint64_t)n * dtype_size(dt)) + (mode == 0 ? sum(b, (uint64_t)n * dtype_size(dt)) : 0);
     touch_w(y, (uint64_t)n, v > 0 ? 1 : 0);
@@ -161,11 +169,13 @@ class HostDevice final : public Device {
   }
   int compare_count(uint32_t op, uint32_t dt, uint32_t mode, const void* a, const void* b, double, int64_t n,
                     double* out, void*) override {
+    note("compare_count");
     if (op > 5 || dt > 2 || mode > 1 || (mode == 0 && !b)) return kBadArgument;
     *out = sum(a, (uint64_t)n * dtype_size(dt)) + (mode == 0 ? sum(b, (uint64_t)n * dtype_size(dt)) : 0);
     return 0;
   }
   int mask_logical(uint32_t op, const void* a, const void* b, void* y, int64_t n, void*) override {
+    note("mask_logical");
     if (op > 3 || (op < 3 && !b)) return kBadArgument;
     if (op < 3) sum(b, (uint64_t)n);
     copy(y, a, (uint64_t)n);
@@ -173,6 +183,7 @@ class HostDevice final : public Device {
   }
   int where(uint32_t dt, const void* m, uint32_t flags, const void* a, const void* b, double, double, void* y,
             int64_t n, void*) override {
+    note("where");
     if (dt > 2 || (flags & ~3u) || (!(flags & 1) && !a) || (!(flags & 2) && !b)) return kBadArgument;
     const uint64_t nb = (uint64_t)n * dtype_size(dt);
     double v = sum(m, (uint64_t)n);
@@ -182,6 +193,7 @@ class HostDevice final : public Device {
     return 0;
   }
   int compress(uint32_t dt, const void* x, const void* m, int64_t n, void* y, int64_t cap, void*) override {
+    note("compress");
     const uint64_t es = dt == kDtBool ? 1 : dt <= 2 ? (uint64_t)dtype_size(dt) : 0;
     if (!es || cap < 0) return kBadArgument;
     const double v = sum(x, (uint64_t)n * es) + sum(m, (uint64_t)n);
@@ -214,6 +226,7 @@ class HostDevice final : public Device {
   }
   int select(uint32_t dt, const void* x, int64_t n, const int64_t* ranks, uint32_t nranks, double* out,
              void*) override {
+    note("select");
     std::vector<double> v;
     if (!widen_all(dt, x, n, &v) || n < 1 || nranks < 1 || nranks > kMaxRanks) return kBadArgument;
     // numpy's sort order: NaNs last
@@ -229,6 +242,7 @@ class HostDevice final : public Device {
   }
   int histogram(uint32_t dt, const void* x, int64_t n, const double* edges, uint32_t bins, uint64_t* counts,
                 void*) override {
+    note("histogram");
     std::vector<double> v;
     if (!widen_all(dt, x, n, &v) || bins < 1 || bins > kMaxBins) return kBadArgument;
     for (uint32_t i = 0; i < bins; ++i) counts[i] = 0;
@@ -241,12 +255,15 @@ class HostDevice final : public Device {
     return 0;
   }
   int rand_reduce(uint32_t op, uint32_t dt, int64_t n, uint64_t, uint64_t, double, double, double* out, void*) override {
+    note("rand_reduce");
     if (op > 1 || dt > 1) return kBadArgument;
     *out = (double)n;
     return 0;
   }
+  void set_lane(void*, bool priority) override { lane_ = priority; }
   int gemm(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc, float, float beta,
            int odt, void*) override {
+    note("gemm");
     // every row of every operand, exactly the bytes the kernel addresses
     for (int i = 0; i < M; ++i) sum((const char*)A + (uint64_t)i * lda * 2, (uint64_t)K * 2);
     for (int j = 0; j < N; ++j) sum((const char*)Bt + (uint64_t)j * ldb * 2, (uint64_t)K * 2);
@@ -260,6 +277,7 @@ class HostDevice final : public Device {
   }
   int gemm_nn(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, float, float beta,
               int odt, void*) override {
+    note("gemm_nn");
     // the device's [K][N] kernel takes tile-multiple shapes only (bk_gemm_bf16_nn_ok)
     if (M % 256 || N % 256 || K % 64) return kBadArgument;
     for (int i = 0; i < M; ++i) sum((const char*)A + (uint64_t)i * lda * 2, (uint64_t)K * 2);
@@ -274,6 +292,7 @@ class HostDevice final : public Device {
   }
   int gemm_fp(uint32_t dt, bool ta, bool tb, const void* A, const void* B, void* C, int M, int N, int K, int64_t lda,
               int64_t ldb, int64_t ldc, void*) override {
+    note("gemm_fp");
     const uint64_t es = dtype_size(dt);
     const int ar = ta ? K : M, ac = ta ? M : K, br = tb ? N : K, bc = tb ? K : N;
     for (int i = 0; i < ar; ++i) sum((const char*)A + (uint64_t)i * lda * es, (uint64_t)ac * es);
@@ -288,6 +307,7 @@ class HostDevice final : public Device {
     return gemm_fp(0, ta, tb, A, B, C, M, N, K, lda, ldb, ldc, s);
   }
   int transpose(int sdt, int ddt, const void* in, void* out, int rows, int cols, int ldi, int ldo, void*) override {
+    note("transpose");
     const uint64_t si = dtype_size((uint32_t)sdt), so = dtype_size((uint32_t)ddt);
     for (int i = 0; i < rows; ++i) sum((const char*)in + (uint64_t)i * ldi * si, (uint64_t)cols * si);
     for (int j = 0; j < cols; ++j) touch_w((char*)out + (uint64_t)j * ldo * so, (uint64_t)rows * so, 0);
@@ -295,6 +315,7 @@ class HostDevice final : public Device {
   }
   int reduce_axis(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,
                   uint32_t axis, void*) override {
+    note("reduce_axis");
     if (op > 1 || axis > 1 || dt > 2) return kBadArgument;
     if (axis == 0 && cols > 262144) return kBadArgument;  // the device's column workspace (reduce.hip)
     const uint64_t es = dtype_size(dt), os = dt == 1 ? 8 : 4;
@@ -337,6 +358,7 @@ class HostDevice final : public Device {
   }
   int broadcast(uint32_t op, uint32_t dt, uint32_t kind, bool swapped, const void* a, const void* v, void* y,
                 int64_t rows, int64_t cols, int64_t lda, int64_t ldy, void*) override {
+    note("broadcast");
     if (op > 6 || dt > 1 || kind > 1 || rows < 0 || cols < 0 || lda < cols || ldy < cols) return kBadArgument;
     if (dt == 1) broadcast_t<double>(op, kind, swapped, a, v, y, rows, cols, lda, ldy);
     else broadcast_t<float>(op, kind, swapped, a, v, y, rows, cols, lda, ldy);
@@ -367,6 +389,7 @@ class HostDevice final : public Device {
   }
   int axis_stat(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld, uint32_t axis,
                 double divisor, void*) override {
+    note("axis_stat");
     if (op > 3 || dt > 1 || axis > 1 || rows <= 0 || cols <= 0 || ld < cols || !(divisor > 0)) return kBadArgument;
     if (axis == 0 && cols > 262144) return kBadArgument;  // the device's column workspace (axis.hip)
     if (dt == 1) axis_stat_t<double>(op, x, y, rows, cols, ld, axis, divisor);
@@ -396,6 +419,16 @@ class HostDevice final : public Device {
   static void copy(void* d, const void* s, uint64_t n) {
     if (n) memmove(d, s, n);
   }
+  // BEE_FUZZ_LAUNCH_LOG=1: one stdout line per launch, "LAUNCH <issue order> <lane> <kernel>"
+  // (lane 1 = priority), for tests/test_broker_plan_cpu.py
+  void note(const char* kernel) {
+    if (!log_) return;
+    printf("LAUNCH %llu %d %s\n", (unsigned long long)launches_++, lane_ ? 1 : 0, kernel);
+    fflush(stdout);
+  }
+  const bool log_ = getenv("BEE_FUZZ_LAUNCH_LOG") && getenv("BEE_FUZZ_LAUNCH_LOG")[0] == '1';
+  unsigned long long launches_ = 0;
+  bool lane_ = false;
   uint64_t budget_, used_ = 0;
   int stream_ = 0;
   std::vector<std::pair<void*, uint64_t>> sizes_;
@@ -422,8 +455,16 @@ int serve_socket(const char* path, HostDevice& dev, int64_t quota) {
     Session s(dev, Peer{[quota] { return quota; }, std::make_shared<Account>()}, &live);
     FrameReader reader(fd);
     std::vector<char> payload, reply;
+    std::vector<FrameView> batch;
+    size_t planned = 0;
     uint32_t hdr[4];
-    while (reader.next(hdr, &payload)) {
+    for (;;) {  // the daemon's loop (broker.cpp serve)
+      if (planned == 0 && reader.batch(&batch)) {
+        s.plan(batch);
+        planned = batch.size();
+      }
+      if (!reader.next(hdr, &payload)) break;
+      if (planned) planned--;
       frames_seen++;
       bool sent = false;
       const int32_t st = s.handle(hdr[0], hdr[1], payload.data(), payload.size(), &reply, &sent);
@@ -459,9 +500,20 @@ int main(int argc, char** argv) {
     Session b(dev, Peer{[quota] { return quota; }, account}, &live);
     std::vector<char> payload, reply;
     FrameReader reader(0, 16u << 20);  // the daemon's reader, over the stdin pipe
+    std::vector<FrameView> batch;
+    size_t planned = 0;
     while (true) {
       uint32_t hdr[4];
       bool too_large = false;
+      // the batch walk over the same hostile bytes; the first session plans
+      // the batches that are all its own
+      if (planned == 0 && reader.batch(&batch)) {
+        bool own = true;
+        for (const FrameView& f : batch) own &= (f.flags & 0x80000000u) == 0;
+        if (own) a.plan(batch);
+        planned = batch.size();
+      }
+      if (planned) planned--;
       if (!reader.next(hdr, &payload, &too_large)) {
         if (too_large) printf("%u frame-too-large\n", hdr[0]);
         break;

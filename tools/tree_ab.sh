@@ -3,12 +3,13 @@
 # checkout built in-tree under the repo (e.g. `git worktree add abtree_r5
 # <commit>` + its own build()).  Appends labelled JSON lines to
 # gpurun_out/tree_ab.jsonl.   bash tools/tree_ab.sh DIR STEPS ROUNDS [WARMUP]
+# ORDER="other this": the other tree runs first in every round (default: this one)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OTHER=$1; STEPS=$2; ROUNDS=$3; WARMUP=${4:-20}
 OUT=$R/gpurun_out/tree_ab.jsonl
 for round in $(seq 1 "$ROUNDS"); do
-  for tree in this other; do
+  for tree in ${ORDER:-this other}; do
     dir=$R; [ "$tree" = other ] && dir=$R/$OTHER
     echo "[tree_ab] round $round $tree" >&2
     # --full: CPU / GPU time per Execute, the materialised run and the executors' figures recorded below
