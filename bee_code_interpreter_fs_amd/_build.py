@@ -68,7 +68,7 @@ def _targets() -> List[Target]:
             compiler=HIPCC,
             compile_flags=HIP_FLAGS,
             link_flags=[f"--offload-arch={ARCH}", "-shared", "-fPIC"],
-            headers=[os.path.join(k, f) for f in ("beekern.h", "bk_common.hpp", "bk_dispatch.hpp", "bk_philox.hpp", "bk_ticket.hpp", "bk_binary_op.hpp", "gemm256_impl.hpp", "gemm256w4_impl.hpp")],
+            headers=[os.path.join(k, f) for f in ("beekern.h", "bk_common.hpp", "bk_dispatch.hpp", "bk_philox.hpp", "bk_ticket.hpp", "bk_reduce_ops.hpp", "bk_binary_op.hpp", "gemm256_impl.hpp", "gemm256w4_impl.hpp")],
             hip=True,
         ),
     ]

@@ -111,6 +111,16 @@ SIGNATURES = {
     "bk_histogram_max_bins": ([], c_int),
     "bk_histogram": ([c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp], c_int),
     "bk_reduce_axis": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp], c_int),
+    "bk_reduce_axis_cast": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_int, c_vp, c_vp, c_vp], c_int),
+    "bk_reduce_axis_tail": (
+        [c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+        c_int,
+    ),
+    "bk_gemm_bf16_tn_tail": (
+        [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_int, c_int, c_vp, c_vp, c_i64, c_vp,
+         c_vp, c_vp],
+        c_int,
+    ),
     "bk_broadcast": ([c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp], c_int),
     "bk_axis_stat": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_d, c_vp, c_vp, c_vp], c_int),
     "bk_gemm_bf16_fast_ok": ([c_int, c_int, c_int, c_int, c_int], c_int),

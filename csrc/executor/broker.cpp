@@ -20,7 +20,8 @@
 namespace bee {
 
 // (broker_core.hpp stays HIP-free and keeps its own copies of the limits)
-static_assert(broker::kMaxBins == BK_MAX_BINS && broker::kMaxRanks == BK_MAX_RANKS,
+static_assert(broker::kMaxBins == BK_MAX_BINS && broker::kMaxRanks == BK_MAX_RANKS &&
+                  broker::kTailMaxVectors == BK_TAIL_MAX_VECTORS,
               "broker_core.hpp and csrc/kernels/beekern.h disagree on a limit");
 
 namespace {
@@ -54,7 +55,8 @@ class HipDevice final : public broker::Device {
   X(compare) X(compare_count) X(mask_logical) X(where) X(compress) /* boolean masks (mask.hip) */                    \
   X(select) X(histogram)                                           /* order statistics, histograms (stats.hip) */    \
   X(broadcast) X(axis_stat)                                        /* matrix against vector, axis statistics (axis.hip) */ \
-  X(rand_dist)                                                     /* continuous distributions (random.hip) */
+  X(rand_dist)                                                     /* continuous distributions (random.hip) */ \
+  X(reduce_axis_cast) X(reduce_axis_tail) X(gemm_bf16_tn_tail)     /* a producer with its cast or closing reduce */
   struct Bk {
 #define X(name) decltype(&bk_##name) name = nullptr;
     BEE_BK_ENTRY_POINTS(X)
@@ -521,6 +523,39 @@ class HipDevice final : public broker::Device {
     // ~10 us -- short next to the GEMM that produced it
     return timed(s, st(s),
                  [&](hipStream_t q) { return bk.reduce_axis((int)op, (int)dt, x, rows, cols, ld, (int)axis, y, ws, q); });
+  }
+  // the fused pairs of a batch (broker_core.hpp Session::plan): one launch, one
+  // op of the GPU-timing segment.  The kernel library answers kBadArgument
+  // where it has no such launch, before launching anything.
+  int reduce_axis_cast(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,
+                       uint32_t axis, uint32_t cdt, void* cy, void* s) override {
+    void* ws = workspace((Ctx*)s, BK_WS_REDUCE_AXIS);
+    if (!ws) return broker::kOutOfMemory;
+    return timed(s, st(s), [&](hipStream_t q) {
+      return bk.reduce_axis_cast((int)op, (int)dt, x, rows, cols, ld, (int)axis, y, (int)cdt, cy, ws, q);
+    });
+  }
+  int reduce_axis_reduce(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,
+                         uint32_t axis, uint32_t rop, const void* a, const void* b, int64_t n, double* out,
+                         void* s) override {
+    Ctx* c = (Ctx*)s;
+    void* ws = workspace(c, BK_WS_REDUCE_AXIS);
+    if (!ws) return broker::kOutOfMemory;
+    const int rc = timed(s, st(s), [&](hipStream_t q) {
+      return bk.reduce_axis_tail((int)op, (int)dt, x, rows, cols, ld, (int)axis, y, ws, (int)rop, a, b, n,
+                                 c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
+    });
+    return fetch(c, rc, out);
+  }
+  int gemm_reduce(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc, float alpha,
+                  float beta, int odt, uint32_t rop, const void* a, const void* b, int64_t n, double* out,
+                  void* s) override {
+    Ctx* c = (Ctx*)s;
+    const int rc = timed(s, st(s), [&](hipStream_t q) {
+      return bk.gemm_bf16_tn_tail(A, Bt, C, M, N, K, lda, ldb, ldc, alpha, beta, odt, (int)rop, a, b, n,
+                                  c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
+    });
+    return fetch(c, rc, out);
   }
   int broadcast(uint32_t op, uint32_t dt, uint32_t kind, bool swapped, const void* a, const void* v, void* y,
                 int64_t rows, int64_t cols, int64_t lda, int64_t ldy, void* s) override {

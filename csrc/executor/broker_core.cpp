@@ -300,9 +300,14 @@ int32_t Session::handle(uint32_t op, uint32_t flags, const char* payload, uint64
   reply->clear();
   const bool no_reply = (flags & kNoReply) != 0;
   *send = !no_reply;
+  frame_ = batch_done_ < pair_q_.size() ? batch_done_++ : SIZE_MAX;
+  // a held producer waits for its partner past allocations only; anything
+  // else in between (the plan allows nothing else) gets it launched first
+  if (held_.op && !(frame_ == held_.q || (frame_ < held_.q && op == kAllocAt))) launch_held();
   if (!no_reply && deferred_st_ != kOk) {
     // an earlier fire-and-forget request failed: report it at this sync
     // point (GPU-style asynchronous error) without running this request
+    launch_held();
     const int32_t st = deferred_st_;
     reply->assign(deferred_msg_.begin(), deferred_msg_.end());
     deferred_st_ = kOk;
@@ -313,6 +318,7 @@ int32_t Session::handle(uint32_t op, uint32_t flags, const char* payload, uint64
   waited_ = false;
   if (frame_weight(op, payload, len) != kNoLaunch) drained_ = false;
   int32_t st = dispatch(op, payload, len, reply);
+  if (held_.op && !(frame_ < held_.q)) launch_held();  // (a partner that failed its validation has not taken it)
   if (waited_) drained_ = true;
   // buffers a successful op overwrote end to end are clean; after a failed
   // one they keep their stale bytes (another tenant's, from the shared
@@ -326,6 +332,7 @@ int32_t Session::handle(uint32_t op, uint32_t flags, const char* payload, uint64
   }
   if (no_reply) {
     if (st != kOk && deferred_st_ == kOk) {
+      deferred_while_held_ = held_.op != 0;
       deferred_st_ = st;
       deferred_msg_ = std::string("deferred from ") + op_name(op);
       if (!reply->empty()) deferred_msg_ += ": " + std::string(reply->begin(), reply->end());
@@ -335,7 +342,78 @@ int32_t Session::handle(uint32_t op, uint32_t flags, const char* payload, uint64
   return st;
 }
 
+namespace {
+// what a producer frame's payload says it reads and writes (nothing validated)
+struct Produces {
+  uint64_t out = 0, in0 = 0, in1 = 0;  // handles
+  uint32_t dt = 0;                     // of the output
+  int64_t count = -1;                  // elements of the output; < 0: no producer the plan pairs
+};
+Produces producer_of(const FrameView& f) {
+  Produces p;
+  Reader r{f.payload, f.len};
+  if (f.op == kReduceAxis) {
+    r.get<uint32_t>();
+    const uint32_t dt = r.get<uint32_t>();
+    p.in0 = p.in1 = r.get<uint64_t>();
+    p.out = r.get<uint64_t>();
+    const int64_t rows = r.get<int64_t>(), cols = r.get<int64_t>();
+    r.get<int64_t>();
+    const uint32_t axis = r.get<uint32_t>();
+    p.dt = dt == 1 ? 1 : 0;
+    if (r.ok && rows > 0 && cols > 0 && axis <= 1) p.count = axis == 0 ? cols : rows;
+  } else if (f.op == kGemm) {
+    p.in0 = r.get<uint64_t>(), p.in1 = r.get<uint64_t>(), p.out = r.get<uint64_t>();
+    const int32_t M = r.get<int32_t>(), N = r.get<int32_t>();
+    r.get<int32_t>(), r.get<int32_t>(), r.get<int32_t>();
+    const int32_t ldc = r.get<int32_t>();
+    r.get<float>();
+    const float beta = r.get<float>();
+    const int32_t odt = r.get<int32_t>();
+    const uint32_t gflags = r.get<uint32_t>();
+    p.dt = (uint32_t)odt;
+    // the skinny kernel's products, every element of C written and none read
+    if (r.ok && gflags == 0 && M > 0 && N > 0 && N <= 16 && ldc == N && beta == 0.f && (odt == 0 || odt == 2))
+      p.count = (int64_t)M * N;
+  }
+  return p;
+}
+// the frame is a cast or a reduction the plan fuses with producer p
+bool consumes(const FrameView& f, const Produces& p) {
+  Reader r{f.payload, f.len};
+  if (f.op == kCast) {
+    const uint32_t s = r.get<uint32_t>(), d = r.get<uint32_t>();
+    const uint64_t x = r.get<uint64_t>(), y = r.get<uint64_t>();
+    const int64_t n = r.get<int64_t>();
+    return r.ok && x == p.out && s == p.dt && n == p.count && d <= 2 && d != s && y != p.out && y != p.in0 && y != p.in1;
+  }
+  if (f.op == kReduce) {
+    const uint32_t rop = r.get<uint32_t>(), dt = r.get<uint32_t>();
+    const uint64_t a = r.get<uint64_t>(), b = r.get<uint64_t>();
+    const int64_t n = r.get<int64_t>();
+    if (!r.ok || rop > 6 || dt != p.dt || n != p.count || !tail_reduce_ok(dt, n)) return false;
+    return rop == 5 || rop == 6 ? (a == p.out) != (b == p.out) : a == p.out;
+  }
+  return false;
+}
+}  // namespace
+
 void Session::plan(const std::vector<FrameView>& batch) {
+  static const bool fuse = !env_off("BEE_BROKER_FUSE");
+  launch_held();  // (nothing is held between batches)
+  pair_q_.assign(fuse ? batch.size() : 0, 0);
+  batch_done_ = 0;
+  for (size_t i = 0; i + 1 < pair_q_.size(); ++i) {
+    if (batch[i].op != kReduceAxis && batch[i].op != kGemm) continue;
+    const Produces p = producer_of(batch[i]);
+    if (p.count < 0) continue;
+    size_t q = i + 1;
+    while (q < batch.size() && batch[q].op == kAllocAt) ++q;
+    if (q < batch.size() && consumes(batch[q], p)) {
+      pair_q_[i] = q;
+      i = q;  // (a consumer produces nothing the plan pairs)
+    }
+  }
   static const bool lanes = !env_off("BEE_BROKER_LANES");
   if (!lanes || !drained_) return;
   bool launches = false, all_short = true;
@@ -349,6 +427,65 @@ void Session::plan(const std::vector<FrameView>& batch) {
     dev_.set_lane(stream_, want);
     lane_ = want;
   }
+}
+
+void Session::hold(Held h) {
+  h.q = pair_q_[frame_];
+  // handle() marks these clean when this frame returns kOk, as after a launch;
+  // launch_held() takes that back if the launch then fails
+  h.clean = pending_clean_;
+  held_ = std::move(h);
+}
+
+void Session::launch_held() {
+  if (!held_.op) return;
+  Held h = std::move(held_);
+  held_ = Held{};
+  const int rc = h.op == kReduceAxis
+                     ? dev_.reduce_axis(h.rop, h.dt, h.x, h.y, h.rows, h.cols, h.ld, h.axis, stream_)
+                     : dev_.gemm(h.x, h.bt, h.y, h.M, h.N, h.K, h.lda, h.ldb, h.ldc, h.alpha, h.beta, h.odt, stream_);
+  if (rc == kOk) return;
+  // what its own frame would have done with the failure: the outputs keep
+  // their stale bytes, and the status is deferred -- ahead of any failure of
+  // a frame handled since
+  for (Buf* b : h.clean) b->clean = false;
+  if (deferred_st_ != kOk && !deferred_while_held_) return;
+  deferred_st_ = rc;
+  deferred_while_held_ = false;
+  deferred_msg_ = std::string("deferred from ") + op_name(h.op);
+  if (rc == kLaunchFailed || rc == kBadArgument) {
+    const char* e = dev_.last_error();
+    if (*e) deferred_msg_ += std::string(": ") + e;
+  }
+}
+
+bool Session::fuse_cast(uint32_t s, uint32_t d, Buf* bx, Buf* by, int64_t n) {
+  const Held& h = held_;
+  if (h.op == kReduceAxis && bx->ptr == h.y && s == h.out_dt && n == h.count && d <= 2 && d != s && by->ptr != h.y &&
+      by->ptr != h.x &&
+      dev_.reduce_axis_cast(h.rop, h.dt, h.x, h.y, h.rows, h.cols, h.ld, h.axis, d, by->ptr, stream_) == kOk) {
+    held_ = Held{};
+    return true;
+  }
+  launch_held();
+  return false;
+}
+
+bool Session::fuse_reduce(uint32_t rop, uint32_t dt, Buf* ba, Buf* bb, int64_t n, double* v) {
+  const Held& h = held_;
+  const void *a = ba->ptr, *b = bb ? bb->ptr : nullptr;
+  if (dt == h.out_dt && n == h.count && tail_reduce_ok(dt, n) && (a == h.y) != (bb && b == h.y)) {
+    const int rc = h.op == kReduceAxis ? dev_.reduce_axis_reduce(h.rop, h.dt, h.x, h.y, h.rows, h.cols, h.ld, h.axis, rop,
+                                                                 a, b, n, v, stream_)
+                                       : dev_.gemm_reduce(h.x, h.bt, h.y, h.M, h.N, h.K, h.lda, h.ldb, h.ldc, h.alpha,
+                                                          h.beta, h.odt, rop, a, b, n, v, stream_);
+    if (rc == kOk) {
+      held_ = Held{};
+      return true;
+    }
+  }
+  launch_held();
+  return false;
 }
 
 int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::vector<char>* out) {
@@ -484,6 +621,10 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
           !mul_ok((uint64_t)n, dtype_size(d), &nout) || !bx || !by || nin > bx->size || nout > by->size)
         return kBadHandle;
       if (!will_read(bx) || !will_write(by, 0, nout)) return kLaunchFailed;
+      if (held_.op) {  // the partner of a held producer (handle() lets no other frame get here)
+        if (fuse_cast(s, d, bx, by, n)) return kOk;
+        if (!will_read(bx)) return kLaunchFailed;  // (a producer that failed when launched left bx stale)
+      }
       return dev_.cast(s, d, bx->ptr, by->ptr, n, stream_);
     }
     case kFill: {
@@ -514,6 +655,14 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
         return kBadHandle;
       if (!will_read(ba) || !will_read(bb)) return kLaunchFailed;
       double v = 0;
+      if (held_.op) {  // the partner of a held producer
+        if (fuse_reduce(rop, dt, ba, bb, n, &v)) {
+          waited_ = true;
+          put(out, v);
+          return kOk;
+        }
+        if (!will_read(ba) || !will_read(bb)) return kLaunchFailed;  // (a producer that failed when launched)
+      }
       const int rc = dev_.reduce(rop, dt, ba->ptr, bb ? bb->ptr : nullptr, n, &v, stream_);
       waited_ = rc == 0;
       put(out, v);
@@ -551,6 +700,13 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
       const bool c_full = beta == 0.f && ldc == N;  // every byte of C[0:M*N] written, nothing read
       if (!will_read(ba) || !will_read(bb) || !(c_full ? will_write(bc, 0, nc) : will_read(bc))) return kLaunchFailed;
       if (nn) return dev_.gemm_nn(ba->ptr, bb->ptr, bc->ptr, M, N, K, lda, ldb, ldc, alpha, beta, odt, stream_);
+      if (holds_here()) {  // launched with its partner in the batch (plan)
+        Held h;
+        h.op = kGemm, h.x = ba->ptr, h.bt = bb->ptr, h.y = bc->ptr, h.M = M, h.N = N, h.K = K, h.lda = lda, h.ldb = ldb;
+        h.ldc = ldc, h.alpha = alpha, h.beta = beta, h.odt = odt, h.out_dt = (uint32_t)odt, h.count = (int64_t)M * N;
+        hold(std::move(h));
+        return kOk;
+      }
       return dev_.gemm(ba->ptr, bb->ptr, bc->ptr, M, N, K, lda, ldb, ldc, alpha, beta, odt, stream_);
     }
     case kGemmFp: {  // f64 / f32 product, either operand possibly a transposed view
@@ -609,6 +765,13 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
           !mul_ok((uint64_t)(axis == 0 ? cols : rows), odt_size, &ny) || !bx || !by || nx > bx->size || ny > by->size)
         return kBadHandle;
       if (!will_read(bx) || !will_write(by, 0, ny)) return kLaunchFailed;
+      if (holds_here()) {  // launched with its partner in the batch (plan)
+        Held h;
+        h.op = kReduceAxis, h.rop = rop, h.dt = dt, h.axis = axis, h.x = bx->ptr, h.y = by->ptr, h.rows = rows;
+        h.cols = cols, h.ld = ld, h.out_dt = dt == 1 ? 1 : 0, h.count = axis == 0 ? cols : rows;
+        hold(std::move(h));
+        return kOk;
+      }
       return dev_.reduce_axis(rop, dt, bx->ptr, by->ptr, rows, cols, ld, axis, stream_);
     }
     case kCompare:

@@ -236,6 +236,26 @@ class Device {
   // per-column (axis 0) / per-row (axis 1) sum or mean into y (f64 for f64 x, else f32)
   virtual int reduce_axis(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,
                           uint32_t axis, void* s) = 0;
+  // A producer and the op that consumes its whole output, in one launch (the
+  // pairs Session::plan marks).  Non-zero: nothing was launched, and the
+  // session launches the two one after the other -- kBadArgument where the
+  // device has no such launch for the arguments.
+  // reduce_axis_cast: reduce_axis into y, and cy[i] = y[i] cast to cdt as cast() would.
+  virtual int reduce_axis_cast(uint32_t, uint32_t, const void*, void*, int64_t, int64_t, int64_t, uint32_t, uint32_t,
+                               void*, void*) {
+    return kBadArgument;
+  }
+  // reduce_axis into y / gemm into C, then reduce(rop, the output's dtype, a,
+  // b, n) with one of a and b that output: synchronous like reduce, and *out
+  // has reduce's bits
+  virtual int reduce_axis_reduce(uint32_t, uint32_t, const void*, void*, int64_t, int64_t, int64_t, uint32_t, uint32_t,
+                                 const void*, const void*, int64_t, double*, void*) {
+    return kBadArgument;
+  }
+  virtual int gemm_reduce(const void*, const void*, void*, int, int, int, int, int, int, float, float, int, uint32_t,
+                          const void*, const void*, int64_t, double*, void*) {
+    return kBadArgument;
+  }
   virtual const char* last_error() = 0;
   virtual void info(int64_t v[5]) = 0;  // CUs, total, free bytes, clock kHz, LDS/CU
   virtual std::string arch() = 0;
@@ -330,6 +350,26 @@ class Session {
   // follows the device's current stream (deferred frees, workspace
   // initialisation, the GPU-timing segments) stays correct with no event
   // between them.  BEE_BROKER_LANES=0: always the normal lane.
+  //
+  // It also marks the pairs to fuse: a producer P (a kReduceAxis, or a kGemm
+  // the skinny kernel takes: N <= 16, ldc == N, beta == 0, Bt given [N][K])
+  // and a later consumer Q (a kCast or a kReduce) where
+  //  * Q reads P's whole output: the same handle, the dtype P writes, the
+  //    element count P produces;
+  //  * Q's other operand is not P's output, Q's output neither P's output nor
+  //    one of P's inputs;
+  //  * every frame between the two is a kAllocAt;
+  //  * a kReduce is one bk_reduce runs in a single block (tail_reduce_ok), a
+  //    kCast goes to f32 / f64 / bf16 from another dtype.
+  // handle() then does everything for P but the launch (parsing, handle and
+  // bounds checks, scrubbing, the statuses of today at P's frame), and at Q,
+  // after Q's own unchanged validation, asks the device for the one launch
+  // that does both.  Where Q fails its validation, where its resolved buffers
+  // are not the ones the plan saw, or where the device declines, P is launched
+  // as it would have been and Q handled as ever: a client cannot tell the two
+  // ways apart except by time (a P that fails when it is launched late still
+  // takes the deferred-error slot ahead of the frames handled after it).
+  // Frames outside a batch are never fused.  BEE_BROKER_FUSE=0: no pairs.
   void plan(const std::vector<FrameView>& batch);
 
   int64_t charged() const { return conn_bytes_; }
@@ -348,6 +388,30 @@ class Session {
   int32_t alloc(uint64_t handle, uint64_t nbytes, uint64_t* out_handle);
   int32_t dispatch(uint32_t op, const char* p, uint64_t n, std::vector<char>* out);
 
+  // ---- fused pairs (plan) ----
+  // a producer whose launch waits for its partner: everything its launch
+  // takes, resolved when its own frame was handled
+  struct Held {
+    uint32_t op = 0;  // kReduceAxis or kGemm; 0: nothing is held
+    size_t q = 0;     // the partner's place in the batch
+    uint32_t rop = 0, dt = 0, axis = 0;  // kReduceAxis: x -> y
+    int64_t rows = 0, cols = 0, ld = 0;
+    const void *x = nullptr, *bt = nullptr;  // kGemm: x . bt -> y
+    void* y = nullptr;
+    int M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0, odt = 0;
+    float alpha = 0, beta = 0;
+    uint32_t out_dt = 0;  // what y gets: dtype and element count
+    int64_t count = 0;
+    std::vector<Buf*> clean;  // marked clean at its frame, on the promise of the launch
+  };
+  bool holds_here() const { return frame_ < pair_q_.size() && pair_q_[frame_] != 0; }
+  void hold(Held h);
+  void launch_held();  // on its own, as its frame would have
+  // the one launch for the held producer and this cast / reduce; false: the
+  // producer has been launched on its own and the caller goes on as ever
+  bool fuse_cast(uint32_t s, uint32_t d, Buf* bx, Buf* by, int64_t n);
+  bool fuse_reduce(uint32_t rop, uint32_t dt, Buf* ba, Buf* bb, int64_t n, double* v);
+
   Device& dev_;
   Peer peer_;
   std::atomic<int64_t>* live_;
@@ -363,7 +427,24 @@ class Session {
   bool drained_ = true;    // nothing launched since the last completed wait for all launches
   bool waited_ = false;    // the op being dispatched completed such a wait
   bool lane_ = false;      // on the priority lane
+  // the planned batch: for each of its frames the place of the consumer it is
+  // fused with (0: none), how many of its frames have been handled, the place
+  // of the one being handled (SIZE_MAX outside a batch)
+  std::vector<size_t> pair_q_;
+  size_t batch_done_ = 0;
+  size_t frame_ = SIZE_MAX;
+  Held held_;
+  bool deferred_while_held_ = false;  // deferred_st_ was set by a frame handled after the held producer's
 };
+
+// a kReduce of n elements of dtype dt is one the kernel library runs in a
+// single block (and so can close a producer's launch): at most
+// kTailMaxVectors 16-byte vectors
+constexpr int64_t kTailMaxVectors = 1024;  // = BK_TAIL_MAX_VECTORS of csrc/kernels/beekern.h
+inline bool tail_reduce_ok(uint32_t dt, int64_t n) {
+  const int es = dtype_size(dt);
+  return es > 0 && n >= 0 && n / (16 / es) <= kTailMaxVectors;
+}
 
 }  // namespace broker
 }  // namespace bee

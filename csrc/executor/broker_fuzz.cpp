@@ -136,6 +136,9 @@ class HostDevice final : public Device {
   }
   int cast(uint32_t s, uint32_t d, const void* x, void* y, int64_t n, void*) override {
     note("cast");
+    return do_cast(s, d, x, y, n);
+  }
+  static int do_cast(uint32_t s, uint32_t d, const void* x, void* y, int64_t n) {
     if (s > 2 || d > 2 || s == d) return kBadArgument;
     sum(x, (uint64_t)n * dtype_size(s));
     touch_w(y, (uint64_t)n * dtype_size(d), 1);
@@ -148,6 +151,9 @@ class HostDevice final : public Device {
   }
   int reduce(uint32_t op, uint32_t dt, const void* a, const void* b, int64_t n, double* out, void*) override {
     note("reduce");
+    return do_reduce(op, dt, a, b, n, out);
+  }
+  static int do_reduce(uint32_t op, uint32_t dt, const void* a, const void* b, int64_t n, double* out) {
     if (dt == kDtBool) {  // a mask of n bytes: count, any, all
       if (op != 0 && op != 3 && op != 4) return kBadArgument;
       *out = sum(a, (uint64_t)n);
@@ -264,6 +270,10 @@ class HostDevice final : public Device {
   int gemm(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc, float, float beta,
            int odt, void*) override {
     note("gemm");
+    return do_gemm(A, Bt, C, M, N, K, lda, ldb, ldc, beta, odt);
+  }
+  static int do_gemm(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc, float beta,
+                     int odt) {
     // every row of every operand, exactly the bytes the kernel addresses
     for (int i = 0; i < M; ++i) sum((const char*)A + (uint64_t)i * lda * 2, (uint64_t)K * 2);
     for (int j = 0; j < N; ++j) sum((const char*)Bt + (uint64_t)j * ldb * 2, (uint64_t)K * 2);
@@ -316,6 +326,44 @@ class HostDevice final : public Device {
   int reduce_axis(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,
                   uint32_t axis, void*) override {
     note("reduce_axis");
+    return do_reduce_axis(op, dt, x, y, rows, cols, ld, axis);
+  }
+  // The fused launches (broker_core.hpp): what the two launches do to the host
+  // arrays, under one line of the launch log.  BEE_FUZZ_NO_FUSED=1: a device
+  // without them (the Device defaults).
+  int reduce_axis_cast(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,
+                       uint32_t axis, uint32_t cdt, void* cy, void*) override {
+    const uint32_t ydt = dt == 1 ? 1 : 0;
+    if (no_fused_ || op > 1 || axis > 1 || dt > 2 || (axis == 0 && cols > 262144) || cdt > 2 || cdt == ydt)
+      return kBadArgument;
+    note("reduce_axis+cast");
+    do_reduce_axis(op, dt, x, y, rows, cols, ld, axis);
+    return do_cast(ydt, cdt, y, cy, axis == 0 ? cols : rows);
+  }
+  int reduce_axis_reduce(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,
+                         uint32_t axis, uint32_t rop, const void* a, const void* b, int64_t n, double* out,
+                         void*) override {
+    const uint32_t ydt = dt == 1 ? 1 : 0;
+    if (no_fused_ || op > 1 || axis > 1 || dt > 2 || (axis == 0 && cols > 262144) || rop > 6 || !tail_reduce_ok(ydt, n) ||
+        n != (axis == 0 ? cols : rows) || ((rop == 5 || rop == 6) && !b))
+      return kBadArgument;
+    note("reduce_axis+reduce");
+    do_reduce_axis(op, dt, x, y, rows, cols, ld, axis);
+    return do_reduce(rop, ydt, a, b, n, out);
+  }
+  int gemm_reduce(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc, float,
+                  float beta, int odt, uint32_t rop, const void* a, const void* b, int64_t n, double* out,
+                  void*) override {
+    // the skinny kernel's products: N <= 16, 16-byte rows, C written whole
+    if (no_fused_ || N > 16 || K % 8 || lda % 8 || ldb % 8 || ldc != N || beta != 0.f || rop > 6 ||
+        !tail_reduce_ok((uint32_t)odt, n) || n != (int64_t)M * N || ((rop == 5 || rop == 6) && !b))
+      return kBadArgument;
+    note("gemm+reduce");
+    do_gemm(A, Bt, C, M, N, K, lda, ldb, ldc, beta, odt);
+    return do_reduce(rop, (uint32_t)odt, a, b, n, out);
+  }
+  static int do_reduce_axis(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,
+                            uint32_t axis) {
     if (op > 1 || axis > 1 || dt > 2) return kBadArgument;
     if (axis == 0 && cols > 262144) return kBadArgument;  // the device's column workspace (reduce.hip)
     const uint64_t es = dtype_size(dt), os = dt == 1 ? 8 : 4;
@@ -427,6 +475,7 @@ class HostDevice final : public Device {
     fflush(stdout);
   }
   const bool log_ = getenv("BEE_FUZZ_LAUNCH_LOG") && getenv("BEE_FUZZ_LAUNCH_LOG")[0] == '1';
+  const bool no_fused_ = getenv("BEE_FUZZ_NO_FUSED") && getenv("BEE_FUZZ_NO_FUSED")[0] == '1';
   unsigned long long launches_ = 0;
   bool lane_ = false;
   uint64_t budget_, used_ = 0;

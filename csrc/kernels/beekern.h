@@ -31,6 +31,7 @@ enum {
   BK_MAX_RANKS = 32,                // ranks per bk_select call
   BK_MAX_BINS = 4096,               // bins per bk_histogram call
   BK_MAX_AXIS0_COLUMNS = 1 << 18,   // columns bk_reduce_axis / bk_axis_stat reduce along axis 0
+  BK_TAIL_MAX_VECTORS = 1024,       // 16-B vectors of a closing reduction's operand (bk_reduce_axis_tail)
 };
 
 // ---- ticketed scratch workspaces -------------------------------------------------
@@ -163,6 +164,23 @@ BK_API int bk_rand_reduce(int op, int dtype, int64_t n, uint64_t seed, uint64_t 
 // and bf16 input (f64 accumulation throughout).  ws: BK_WS_REDUCE_AXIS.
 BK_API int bk_reduce_axis(int op, int dtype, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis, void* out,
                           void* ws, hipStream_t stream);
+// bk_reduce_axis, and cast_out[i] = out[i] converted to cast_dtype (kF32, kF64
+// or kBF16, another dtype than out's) exactly as bk_cast converts it: the bits
+// of bk_reduce_axis followed by bk_cast, in one launch.  out is written too.
+// cast_out is another buffer than out and x.
+BK_API int bk_reduce_axis_cast(int op, int dtype, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis,
+                               void* out, int cast_dtype, void* cast_out, void* ws, hipStream_t stream);
+// bk_reduce_axis, and then what bk_reduce(tail_op, out's dtype, tail_a, tail_b,
+// tail_n, tail_ws, tail_out) would store, in one launch: the last block to
+// finish reduces.  One of tail_a and tail_b (tail_a for a one-operand op) is
+// `out`, the other a buffer no part of this launch writes; tail_n is the
+// number of elements out gets and spans at most BK_TAIL_MAX_VECTORS 16-byte
+// vectors (where bk_reduce runs a single block: the scalar then has its
+// bits); tail_ws: BK_WS_REDUCE.  kBadArgument, with nothing launched, where
+// there is no such tail: launch bk_reduce_axis and bk_reduce instead.
+BK_API int bk_reduce_axis_tail(int op, int dtype, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis,
+                               void* out, void* ws, int tail_op, const void* tail_a, const void* tail_b, int64_t tail_n,
+                               void* tail_ws, void* tail_out, hipStream_t stream);
 
 // ---- boolean masks (mask.hip): one byte per element ------------------------------------------
 // mode: 0 = array (op) array, 1 = array (op) scalar; mask_out: n bytes of 0 / 1
@@ -232,6 +250,14 @@ BK_API int bk_gemm_bf16_tn(const void* A, const void* Bt, void* C, int M, int N,
 // kernel cannot take the operands.
 BK_API int bk_gemm_bf16_tn_variant(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb,
                                    int ldc, float alpha, float beta, int out_dtype, int variant, hipStream_t stream);
+// The skinny product (N <= 16, what variant 0 picks for such operands) with
+// beta == 0 and ldc == N, and then bk_reduce(tail_op, out_dtype, tail_a,
+// tail_b, tail_n = M * N, tail_ws, tail_out) in the same launch: the rules of
+// bk_reduce_axis_tail, with C as the produced buffer.  kBadArgument, with
+// nothing launched, for any other product or tail.
+BK_API int bk_gemm_bf16_tn_tail(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc,
+                                float alpha, float beta, int out_dtype, int tail_op, const void* tail_a,
+                                const void* tail_b, int64_t tail_n, void* tail_ws, void* tail_out, hipStream_t stream);
 // Which kernel `variant 0` resolves to for these operands (diagnostics).
 BK_API int bk_gemm_bf16_pick(const void* A, const void* Bt, const void* C, int M, int N, int K, int lda, int ldb,
                              int ldc, int out_dtype);

@@ -17,6 +17,7 @@
 // Generic path: any shape / alignment, 64x64x32 tile, guarded register
 // staging with zero fill.  Same MFMA and fragment maps, slower.
 #include "bk_common.hpp"
+#include "bk_reduce_ops.hpp"  // the output policies of the skinny kernel, the closing reduction
 
 namespace bk {
 
@@ -271,6 +272,103 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// The rows row0, row0 + 1 of one wave (row0 < M) for the kernel that closes
+// with a reduction of C: gemm_bf16_tn_skinny's, with the stores left to X
+// (bk_reduce_ops.hpp TailOut<OP>).
+template <bool OUT_BF16, class X>
+__device__ __forceinline__ void skinny_rows(const uint16_t* A, const uint16_t* Bt,
+                                            void* C, int M, int r, int K, int lda, int ldb, int ldc,
+                                            float alpha, float beta, int lane, int64_t row0, X ext) {
+  float acc[kSkinnyRows][kSkinnyCols];
+#pragma unroll
+  for (int i = 0; i < kSkinnyRows; ++i)
+#pragma unroll
+    for (int j = 0; j < kSkinnyCols; ++j) acc[i][j] = 0.f;
+  // four K steps' loads in flight per lane (the GEMV shape is latency-bound:
+  // 4096^2 . 4096 ran 9.4 us with one step at a time); the FMAs still run
+  // step by step, so the sums are the one-step loop's
+  constexpr int KB = 4;
+  int k = lane * 8;
+  for (; k + (KB - 1) * 512 < K; k += KB * 512) {
+    uint4 qa[KB][kSkinnyRows];
+#pragma unroll
+    for (int s = 0; s < KB; ++s)
+#pragma unroll
+      for (int i = 0; i < kSkinnyRows; ++i) {
+        const int64_t row = min(row0 + i, (int64_t)M - 1);
+        qa[s][i] = *reinterpret_cast<const uint4*>(A + row * lda + k + s * 512);
+      }
+#pragma unroll
+    for (int j = 0; j < kSkinnyCols; ++j) {
+      if (j >= r) break;
+      uint4 qb[KB];
+#pragma unroll
+      for (int s = 0; s < KB; ++s) qb[s] = *reinterpret_cast<const uint4*>(Bt + (int64_t)j * ldb + k + s * 512);
+#pragma unroll
+      for (int s = 0; s < KB; ++s) {
+        const uint32_t wb[4] = {qb[s].x, qb[s].y, qb[s].z, qb[s].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float b0 = bf16_bits_to_float((uint16_t)(wb[e] & 0xffff)), b1 = bf16_bits_to_float((uint16_t)(wb[e] >> 16));
+#pragma unroll
+          for (int i = 0; i < kSkinnyRows; ++i) {
+            const uint32_t wa = e == 0 ? qa[s][i].x : e == 1 ? qa[s][i].y : e == 2 ? qa[s][i].z : qa[s][i].w;
+            acc[i][j] += bf16_bits_to_float((uint16_t)(wa & 0xffff)) * b0 + bf16_bits_to_float((uint16_t)(wa >> 16)) * b1;
+          }
+        }
+      }
+    }
+  }
+  for (; k < K; k += 512) {  // K % 8 == 0: chunks are whole
+    float a[kSkinnyRows][8];
+#pragma unroll
+    for (int i = 0; i < kSkinnyRows; ++i) {
+      const int64_t row = min(row0 + i, (int64_t)M - 1);  // (a clamped duplicate row is never stored)
+      const uint4 q = *reinterpret_cast<const uint4*>(A + row * lda + k);
+      const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        a[i][2 * e] = bf16_bits_to_float((uint16_t)(w[e] & 0xffff));
+        a[i][2 * e + 1] = bf16_bits_to_float((uint16_t)(w[e] >> 16));
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kSkinnyCols; ++j) {
+      if (j >= r) break;
+      const uint4 q = *reinterpret_cast<const uint4*>(Bt + (int64_t)j * ldb + k);
+      const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float b0 = bf16_bits_to_float((uint16_t)(w[e] & 0xffff)), b1 = bf16_bits_to_float((uint16_t)(w[e] >> 16));
+#pragma unroll
+        for (int i = 0; i < kSkinnyRows; ++i) acc[i][j] += a[i][2 * e] * b0 + a[i][2 * e + 1] * b1;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kSkinnyRows; ++i) {
+    const int64_t row = row0 + i;
+#pragma unroll
+    for (int j = 0; j < kSkinnyCols; ++j) {
+      if (j >= r) break;
+      const float s = wave_sum(acc[i][j]);
+      if (lane == 0 && row < M) {
+        float v = alpha * s;
+        if constexpr (OUT_BF16) {
+          uint16_t* c = (uint16_t*)C + row * ldc + j;
+          if (beta != 0.f) v += beta * bf16_bits_to_float(*c);
+          ext.store(c, 0, float_to_bf16_bits(v));
+        } else {
+          float* c = (float*)C + row * ldc + j;
+          if (beta != 0.f) v += beta * *c;
+          ext.store(c, 0, v);
+        }
+      }
+    }
+  }
+}
+// (the plain kernel keeps its own copy of the rows: over skinny_rows the
+// compiler unrolls them differently)
 template <bool OUT_BF16>
 __global__ __launch_bounds__(256) void gemm_bf16_tn_skinny(const uint16_t* __restrict__ A, const uint16_t* __restrict__ Bt,
                                                            void* __restrict__ C, int M, int r, int K, int lda, int ldb,
@@ -365,6 +463,18 @@ __global__ __launch_bounds__(256) void gemm_bf16_tn_skinny(const uint16_t* __res
       }
     }
   }
+}
+// with a tail: every block takes the tail's ticket once its stores are issued
+// (a wave past the last row stays for it); beta == 0
+template <bool OUT_BF16, class X>
+__global__ __launch_bounds__(256) void gemm_bf16_tn_skinny_x(const uint16_t* __restrict__ A,
+                                                             const uint16_t* __restrict__ Bt, void* __restrict__ C, int M,
+                                                             int r, int K, int lda, int ldb, int ldc, float alpha,
+                                                             float beta, X ext) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row0 = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * kSkinnyRows;
+  if (row0 < M) skinny_rows<OUT_BF16>(A, Bt, C, M, r, K, lda, ldb, ldc, alpha, beta, lane, row0, ext);
+  run_tail<typename std::conditional<OUT_BF16, uint16_t, float>::type, X::kOp, 256>(ext.tail, gridDim.x);
 }
 
 // ---- generic path ------------------------------------------------------------
@@ -708,6 +818,26 @@ BK_API int bk_gemm_bf16_tn_variant(const void* A, const void* Bt, void* C, int M
                                                             ldb, ldc, alpha, beta);
   }
   return launch_status();
+}
+
+BK_API int bk_gemm_bf16_tn_tail(const void* A, const void* Bt, void* C, int M, int N, int K, int lda, int ldb, int ldc,
+                                float alpha, float beta, int out_dtype, int tail_op, const void* tail_a,
+                                const void* tail_b, int64_t tail_n, void* tail_ws, void* tail_out, hipStream_t stream) {
+  if (!A || !Bt || !C || M <= 0 || N <= 0 || K <= 0 || lda < K || ldb < K || ldc != N || beta != 0.f) return kBadArgument;
+  if ((out_dtype != kBF16 && out_dtype != kF32) || !skinny_ok(A, Bt, N, K, lda, ldb)) return kBadArgument;
+  if (tail_a == A || tail_a == Bt || tail_b == A || tail_b == Bt) return kBadArgument;
+  const unsigned g = (unsigned)((M + 4 * kSkinnyRows - 1) / (4 * kSkinnyRows));
+  return dispatch_flag(out_dtype == kBF16, [&](auto bf) {
+    constexpr bool BF = decltype(bf)::value;
+    using TO = typename std::conditional<BF, uint16_t, float>::type;
+    Tail t;
+    if (!make_tail<TO>(tail_op, tail_a, tail_b, tail_n, tail_ws, tail_out, C, (int64_t)M * N, &t)) return (int)kBadArgument;
+    return dispatch_op<kRedCount>(tail_op, [&](auto opc) {
+      gemm_bf16_tn_skinny_x<BF, TailOut<decltype(opc)::value>><<<g, 256, 0, stream>>>(
+          (const uint16_t*)A, (const uint16_t*)Bt, C, M, N, K, lda, ldb, ldc, alpha, beta, TailOut<decltype(opc)::value>{t});
+      return launch_status();
+    });
+  });
 }
 
 BK_API int bk_gemm_bf16_pick(const void* A, const void* Bt, const void* C, int M, int N, int K, int lda, int ldb,

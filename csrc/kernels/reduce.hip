@@ -16,14 +16,10 @@
 
 #include "bk_common.hpp"
 #include "bk_philox.hpp"
+#include "bk_reduce_ops.hpp"  // ReduceOp, red_map / red_combine / block_reduce, the closing reduction
 #include "bk_ticket.hpp"  // kRedBlock, kRedBlocks, kRedMaxBlocks, grid_blocks and the completion tickets
 
 namespace bk {
-
-// kRedMaxAbsDiff: max |a - b| (two operands, like kRedDot) -- one pass where
-// subtract + abs + max would be three (e.g. a row check against a reference)
-enum ReduceOp : int { kRedSum = 0, kRedSquareSum, kRedAbsSum, kRedMax, kRedMin, kRedDot, kRedMaxAbsDiff, kRedCount };
-template <int OP> constexpr bool kTwoOperands = OP == kRedDot || OP == kRedMaxAbsDiff;
 
 // kRedMaxBlocks (bk_ticket.hpp) is the stage-1 grid cap and the workspace
 // length: 32 blocks per CU with 16 loads in flight per lane
@@ -45,6 +41,7 @@ template <int OP> constexpr bool kTwoOperands = OP == kRedDot || OP == kRedMaxAb
 // the grid (8 waves per CU), not the bytes in flight, sets the rate, and
 // ~5.8 TB/s (torch.sum's too) is this read stream's ceiling on these boxes
 constexpr int kRedUnroll = 16;
+static_assert(kRedUnroll == kTailUnroll, "run_tail (bk_reduce_ops.hpp) adds in reduce_1pass's order");
 // the fused RNG->reduce kernels are VALU-bound (80% of SIMD cycles issue
 // VALU, profiles/archive/r4_payload_kernels_pmc.csv): 8 blocks per CU (8 waves per
 // SIMD) hide more of each Philox chain's latency -- 1e8 f64 square-sum
@@ -64,49 +61,6 @@ inline int64_t env_int(const char* name, int64_t dflt) {
 inline int64_t grid_knob(const char* name, int64_t dflt) {
   const int64_t v = env_int(name, dflt);
   return v <= kRedMaxBlocks ? v : dflt;
-}
-
-template <int OP> __device__ __forceinline__ double red_init() {
-  if constexpr (OP == kRedMax) return -INFINITY;
-  else if constexpr (OP == kRedMaxAbsDiff) return 0.0;
-  else if constexpr (OP == kRedMin) return INFINITY;
-  else return 0.0;
-}
-template <int OP> __device__ __forceinline__ double red_map(double a, double b) {
-  if constexpr (OP == kRedSquareSum) return a * a;
-  else if constexpr (OP == kRedAbsSum) return fabs(a);
-  else if constexpr (OP == kRedDot) return a * b;
-  else if constexpr (OP == kRedMaxAbsDiff) return fabs(a - b);
-  else return a;
-}
-// max / min propagate NaN as numpy's max() / min() do (fmax / fmin are IEEE
-// maxNum: they drop a NaN operand, so a max-abs-difference check of a result
-// holding NaN would return a finite "error")
-template <int OP> __device__ __forceinline__ double red_combine(double x, double y) {
-  if constexpr (OP == kRedMax || OP == kRedMaxAbsDiff) return (x != x || y != y) ? __builtin_nan("") : fmax(x, y);
-  else if constexpr (OP == kRedMin) return (x != x || y != y) ? __builtin_nan("") : fmin(x, y);
-  else return x + y;
-}
-
-template <int OP> __device__ __forceinline__ double wave_reduce(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = red_combine<OP>(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-
-template <int OP> __device__ __forceinline__ double block_reduce(double v) {
-  constexpr int kWaves = kRedBlock / kWave;
-  __shared__ double partial[kWaves];
-  v = wave_reduce<OP>(v);
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  if (lane == 0) partial[wid] = v;
-  __syncthreads();
-  double r = red_init<OP>();
-  if (wid == 0) {
-    r = lane < kWaves ? partial[lane] : red_init<OP>();
-    r = wave_reduce<OP>(r);
-  }
-  return r;
 }
 
 // ---- single-launch completion (the tickets: bk_ticket.hpp) ----------------------
@@ -488,10 +442,16 @@ __device__ __forceinline__ double fold_chunks(const double* part, int chunks, in
   return (a[0] + a[1]) + (a[2] + a[3]);
 }
 
-template <typename T, typename TO>
-__global__ __launch_bounds__(256) void colsum_1pass(const T* __restrict__ x, int64_t rows, int64_t cols, int64_t ld,
-                                                    int64_t rows_per_chunk, double* __restrict__ part,
-                                                    unsigned* __restrict__ tickets, TO* __restrict__ out, double scale) {
+// Each of the four kernels below comes twice over one body that takes an
+// output policy X (bk_reduce_ops.hpp: PlainOut, CastOut, TailOut): the plain
+// kernel, and the _x one that carries a policy's arguments.  With a tail, a
+// column kernel's strip-last blocks (the ones that store) take the tail's
+// ticket, one per strip; every block of a row kernel does.
+template <typename T, typename TO, class X>
+__device__ __forceinline__ void colsum_1pass_body(const T* x, int64_t rows, int64_t cols, int64_t ld,
+                                                  int64_t rows_per_chunk, double* part,
+                                                  unsigned* tickets, TO* out, double scale,
+                                                  X ext) {
   const int64_t col = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (col < cols) {
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
@@ -506,8 +466,22 @@ __global__ __launch_bounds__(256) void colsum_1pass(const T* __restrict__ x, int
     publish(part + (int64_t)blockIdx.y * cols + col, a0 + a1);
   }
   if (!take_last_ticket(tickets + blockIdx.x, gridDim.y)) return;
-  if (col < cols) out[col] = (TO)(fold_chunks(part, (int)gridDim.y, cols, col) * scale);
+  if (col < cols) ext.store(out, col, (TO)(fold_chunks(part, (int)gridDim.y, cols, col) * scale));
   if (threadIdx.x == 0) rearm(tickets + blockIdx.x);
+  if constexpr (X::kTail) run_tail<TO, X::kOp, 256>(ext.tail, gridDim.x);
+}
+template <typename T, typename TO>
+__global__ __launch_bounds__(256) void colsum_1pass(const T* __restrict__ x, int64_t rows, int64_t cols, int64_t ld,
+                                                    int64_t rows_per_chunk, double* __restrict__ part,
+                                                    unsigned* __restrict__ tickets, TO* __restrict__ out, double scale) {
+  colsum_1pass_body<T, TO>(x, rows, cols, ld, rows_per_chunk, part, tickets, out, scale, PlainOut{});
+}
+template <typename T, typename TO, class X>
+__global__ __launch_bounds__(256) void colsum_1pass_x(const T* __restrict__ x, int64_t rows, int64_t cols, int64_t ld,
+                                                      int64_t rows_per_chunk, double* __restrict__ part,
+                                                      unsigned* __restrict__ tickets, TO* __restrict__ out, double scale,
+                                                      X ext) {
+  colsum_1pass_body<T, TO>(x, rows, cols, ld, rows_per_chunk, part, tickets, out, scale, ext);
 }
 
 // Column sums, 16-B vectors: a block of 16 waves owns a 16*V-column strip
@@ -520,6 +494,68 @@ __global__ __launch_bounds__(256) void colsum_1pass(const T* __restrict__ x, int
 // (completion ticket) folds the strip's chunk partials in chunk order.  Narrow
 // strips keep the chunk count low (4096^2: 32 strips x 32 chunks) -- the
 // 512-column version spent most of its 13.6-15.4 us folding 64 chunks.
+template <typename T, typename TO, class X>
+__device__ __forceinline__ void colsum_tile_v_body(const T* x, int64_t rows, int64_t cols, int64_t ld,
+                                                   int64_t rows_per_chunk, double* part,
+                                                   unsigned* tickets, TO* out, double scale,
+                                                   X ext) {
+  constexpr int V = 16 / sizeof(T);
+  constexpr int W = 16 * V;  // strip width (columns)
+  __shared__ double sacc[kColWaves][W];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int cl = lane & 15, rl = lane >> 4;  // column lane, row lane
+  const int64_t col0 = (int64_t)blockIdx.x * W + cl * V;
+  const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
+  const int64_t r1 = r0 + rows_per_chunk < rows ? r0 + rows_per_chunk : rows;
+  constexpr int kStep = kColWaves * 4;  // rows per block step
+  double acc[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) acc[j] = 0.0;
+  if (col0 < cols) {
+    int64_t r = r0 + wave * 4 + rl;
+    for (; r + 3 * kStep < r1; r += 4 * kStep) {
+      V16<T> v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const V16<T>*>(x + (r + q * kStep) * ld + col0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int j = 0; j < V; ++j) acc[j] += widen<T>(v[q].v[j]);
+    }
+    for (; r < r1; r += kStep) {
+      const V16<T> v = *reinterpret_cast<const V16<T>*>(x + r * ld + col0);
+#pragma unroll
+      for (int j = 0; j < V; ++j) acc[j] += widen<T>(v.v[j]);
+    }
+  }
+  // row lanes 0..3 of each column lane: (0 + 1) + (2 + 3), same in every lane
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    acc[j] += __shfl_xor(acc[j], 16, 64);
+    acc[j] += __shfl_xor(acc[j], 32, 64);
+  }
+  if (rl == 0) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) sacc[wave][cl * V + j] = acc[j];
+  }
+  __syncthreads();
+  if (threadIdx.x < W) {
+    const int64_t col = (int64_t)blockIdx.x * W + threadIdx.x;
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < kColWaves; ++w) s += sacc[w][threadIdx.x];
+    if (col < cols) publish(part + (int64_t)blockIdx.y * cols + col, s);
+  }
+  if (!take_last_ticket(tickets + blockIdx.x, gridDim.y)) return;
+  if (threadIdx.x < W) {
+    const int64_t col = (int64_t)blockIdx.x * W + threadIdx.x;
+    if (col < cols) ext.store(out, col, (TO)(fold_chunks(part, (int)gridDim.y, cols, col) * scale));
+  }
+  if (threadIdx.x == 0) rearm(tickets + blockIdx.x);
+  if constexpr (X::kTail) run_tail<TO, X::kOp, kColWaves * 64>(ext.tail, gridDim.x);
+}
+// (the plain kernel keeps its own copy: over colsum_tile_v_body the compiler
+// addresses the bf16 loads differently)
 template <typename T, typename TO>
 __global__ __launch_bounds__(kColWaves * 64) void colsum_tile_v(const T* __restrict__ x, int64_t rows, int64_t cols,
                                                               int64_t ld, int64_t rows_per_chunk,
@@ -579,21 +615,71 @@ __global__ __launch_bounds__(kColWaves * 64) void colsum_tile_v(const T* __restr
   }
   if (threadIdx.x == 0) rearm(tickets + blockIdx.x);
 }
+template <typename T, typename TO, class X>
+__global__ __launch_bounds__(kColWaves * 64) void colsum_tile_v_x(const T* __restrict__ x, int64_t rows, int64_t cols,
+                                                                int64_t ld, int64_t rows_per_chunk,
+                                                                double* __restrict__ part, unsigned* __restrict__ tickets,
+                                                                TO* __restrict__ out, double scale, X ext) {
+  colsum_tile_v_body<T, TO>(x, rows, cols, ld, rows_per_chunk, part, tickets, out, scale, ext);
+}
 
-template <typename T, typename TO>
-__global__ __launch_bounds__(256) void rowsum(const T* __restrict__ x, int64_t rows, int64_t cols, int64_t ld,
-                                              TO* __restrict__ out, double scale) {
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+// one wave's row (row < rows)
+template <typename T, typename TO, class X>
+__device__ __forceinline__ void rowsum_row(const T* x, int64_t row, int64_t cols, int64_t ld,
+                                           TO* out, double scale, X ext) {
   const int lane = threadIdx.x & 63;
   const T* p = x + row * ld;
   double acc = 0.0;
   for (int64_t c = lane; c < cols; c += 64) acc += widen<T>(p[c]);
   acc = wave_reduce<kRedSum>(acc);
-  if (lane == 0) out[row] = (TO)(acc * scale);
+  if (lane == 0) ext.store(out, row, (TO)(acc * scale));
+}
+template <typename T, typename TO>
+__global__ __launch_bounds__(256) void rowsum(const T* __restrict__ x, int64_t rows, int64_t cols, int64_t ld,
+                                              TO* __restrict__ out, double scale) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  rowsum_row<T, TO>(x, row, cols, ld, out, scale, PlainOut{});
+}
+// (with a tail, a wave past the last row stays for the block's ticket)
+template <typename T, typename TO, class X>
+__global__ __launch_bounds__(256) void rowsum_x(const T* __restrict__ x, int64_t rows, int64_t cols, int64_t ld,
+                                                TO* __restrict__ out, double scale, X ext) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row < rows) rowsum_row<T, TO>(x, row, cols, ld, out, scale, ext);
+  if constexpr (X::kTail) run_tail<TO, X::kOp, 256>(ext.tail, gridDim.x);
 }
 
 // 16-B vectors: a wave reads 1 KiB of its row per step (bf16: 512 columns)
+template <typename T, typename TO, class X>
+__device__ __forceinline__ void rowsum_v_row(const T* x, int64_t row, int64_t cols, int64_t ld,
+                                             TO* out, double scale, X ext) {
+  constexpr int V = 16 / sizeof(T);
+  const int lane = threadIdx.x & 63;
+  const V16<T>* p = reinterpret_cast<const V16<T>*>(x + row * ld);
+  const int64_t nv = cols / V;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  int64_t c = lane;
+  for (; c + 192 < nv; c += 256) {  // four vectors in flight per lane
+    const V16<T> u = p[c], w = p[c + 64], y = p[c + 128], z = p[c + 192];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      a0 += widen<T>(u.v[j]);
+      a1 += widen<T>(w.v[j]);
+      a2 += widen<T>(y.v[j]);
+      a3 += widen<T>(z.v[j]);
+    }
+  }
+  for (; c < nv; c += 64) {
+    const V16<T> u = p[c];
+#pragma unroll
+    for (int j = 0; j < V; ++j) a0 += widen<T>(u.v[j]);
+  }
+  const double acc = wave_reduce<kRedSum>((a0 + a1) + (a2 + a3));
+  if (lane == 0) ext.store(out, row, (TO)(acc * scale));
+}
+// (the plain kernel keeps its own copy of the row: over rowsum_v_row the
+// compiler addresses its loads differently)
 template <typename T, typename TO>
 __global__ __launch_bounds__(256) void rowsum_v(const T* __restrict__ x, int64_t rows, int64_t cols, int64_t ld,
                                                 TO* __restrict__ out, double scale) {
@@ -623,16 +709,29 @@ __global__ __launch_bounds__(256) void rowsum_v(const T* __restrict__ x, int64_t
   const double acc = wave_reduce<kRedSum>((a0 + a1) + (a2 + a3));
   if (lane == 0) out[row] = (TO)(acc * scale);
 }
+template <typename T, typename TO, class X>
+__global__ __launch_bounds__(256) void rowsum_v_x(const T* __restrict__ x, int64_t rows, int64_t cols, int64_t ld,
+                                                  TO* __restrict__ out, double scale, X ext) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row < rows) rowsum_v_row<T, TO>(x, row, cols, ld, out, scale, ext);
+  if constexpr (X::kTail) run_tail<TO, X::kOp, 256>(ext.tail, gridDim.x);
+}
 
-template <typename T, typename TO>
+template <typename T, typename TO, class X = PlainOut>
 int launch_axis(const T* x, int64_t rows, int64_t cols, int64_t ld, int axis, TO* out, double scale, double* ws,
-                hipStream_t s) {
+                hipStream_t s, const X& ext = X{}) {
   constexpr int V = 16 / sizeof(T);
+  constexpr bool kPlain = std::is_same<X, PlainOut>::value;
   if (axis == 1) {
-    if (cols % V == 0 && ld % V == 0 && ((uintptr_t)x & 15) == 0)
-      rowsum_v<T, TO><<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(x, rows, cols, ld, out, scale);
-    else
-      rowsum<T, TO><<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(x, rows, cols, ld, out, scale);
+    const unsigned g = (unsigned)((rows + 3) / 4);
+    const bool vec = cols % V == 0 && ld % V == 0 && ((uintptr_t)x & 15) == 0;
+    if constexpr (kPlain) {
+      if (vec) rowsum_v<T, TO><<<g, 256, 0, s>>>(x, rows, cols, ld, out, scale);
+      else rowsum<T, TO><<<g, 256, 0, s>>>(x, rows, cols, ld, out, scale);
+    } else {
+      if (vec) rowsum_v_x<T, TO, X><<<g, 256, 0, s>>>(x, rows, cols, ld, out, scale, ext);
+      else rowsum_x<T, TO, X><<<g, 256, 0, s>>>(x, rows, cols, ld, out, scale, ext);
+    }
     return launch_status();
   }
   // (strips of 16*V columns while the tickets go round; wider matrices take
@@ -659,11 +758,35 @@ int launch_axis(const T* x, int64_t rows, int64_t cols, int64_t ld, int axis, TO
   unsigned* tickets = reinterpret_cast<unsigned*>(ws + kAxisWsDoubles);
   if (col_blocks > kAxisTickets) return kBadArgument;
   const dim3 grid((unsigned)col_blocks, (unsigned)chunks);
-  if (vec)
-    colsum_tile_v<T, TO><<<grid, kColWaves * 64, 0, s>>>(x, rows, cols, ld, per, ws, tickets, out, scale);
-  else
-    colsum_1pass<T, TO><<<grid, 256, 0, s>>>(x, rows, cols, ld, per, ws, tickets, out, scale);
+  if constexpr (kPlain) {
+    if (vec) colsum_tile_v<T, TO><<<grid, kColWaves * 64, 0, s>>>(x, rows, cols, ld, per, ws, tickets, out, scale);
+    else colsum_1pass<T, TO><<<grid, 256, 0, s>>>(x, rows, cols, ld, per, ws, tickets, out, scale);
+  } else {
+    if (vec) colsum_tile_v_x<T, TO, X><<<grid, kColWaves * 64, 0, s>>>(x, rows, cols, ld, per, ws, tickets, out, scale, ext);
+    else colsum_1pass_x<T, TO, X><<<grid, 256, 0, s>>>(x, rows, cols, ld, per, ws, tickets, out, scale, ext);
+  }
   return launch_status();
+}
+
+// bk_reduce_axis's argument check, its scale and its dispatch on the input dtype:
+// f(x typed, out typed, scale) launches
+inline bool axis_args_ok(int op, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis, const void* out,
+                         const void* ws) {
+  if (!x || !out || !ws || rows <= 0 || cols <= 0 || ld < cols || (axis != 0 && axis != 1) || (op != 0 && op != 1))
+    return false;
+  return !(axis == 0 && cols > kAxisWsDoubles);  // > 262144 columns: reduce a transposed view instead
+}
+inline double axis_scale(int op, int64_t rows, int64_t cols, int axis) {
+  return op == 1 ? 1.0 / (double)(axis == 0 ? rows : cols) : 1.0;
+}
+template <typename F>
+int dispatch_axis_dtype(int dtype, const void* x, void* out, F&& f) {
+  switch (dtype) {
+    case kF64: return f((const double*)x, (double*)out);
+    case kF32: return f((const float*)x, (float*)out);
+    case kBF16: return f((const uint16_t*)x, (float*)out);
+  }
+  return kBadArgument;
 }
 
 // partials, then the completion ticket (its own 256 B)
@@ -721,15 +844,46 @@ BK_API int bk_reduce(int op, int dtype, const void* a, const void* b, int64_t n,
 
 BK_API int bk_reduce_axis(int op, int dtype, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis, void* out,
                           void* ws, hipStream_t stream) {
-  if (!x || !out || !ws || rows <= 0 || cols <= 0 || ld < cols || (axis != 0 && axis != 1) || (op != 0 && op != 1))
+  if (!axis_args_ok(op, x, rows, cols, ld, axis, out, ws)) return kBadArgument;
+  const double scale = axis_scale(op, rows, cols, axis);
+  return dispatch_axis_dtype(dtype, x, out, [&](auto* xt, auto* ot) {
+    return launch_axis(xt, rows, cols, ld, axis, ot, scale, (double*)ws, stream);
+  });
+}
+
+BK_API int bk_reduce_axis_cast(int op, int dtype, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis,
+                               void* out, int cast_dtype, void* cast_out, void* ws, hipStream_t stream) {
+  if (!axis_args_ok(op, x, rows, cols, ld, axis, out, ws) || !cast_out || cast_out == out || cast_out == x)
     return kBadArgument;
-  if (axis == 0 && cols > kAxisWsDoubles) return kBadArgument;  // > 262144 columns: reduce a transposed view instead
-  const double scale = op == 1 ? 1.0 / (double)(axis == 0 ? rows : cols) : 1.0;
-  double* w = (double*)ws;
-  switch (dtype) {
-    case kF64: return launch_axis<double, double>((const double*)x, rows, cols, ld, axis, (double*)out, scale, w, stream);
-    case kF32: return launch_axis<float, float>((const float*)x, rows, cols, ld, axis, (float*)out, scale, w, stream);
-    case kBF16: return launch_axis<uint16_t, float>((const uint16_t*)x, rows, cols, ld, axis, (float*)out, scale, w, stream);
-  }
-  return kBadArgument;
+  const double scale = axis_scale(op, rows, cols, axis);
+  return dispatch_axis_dtype(dtype, x, out, [&](auto* xt, auto* ot) {
+    using TO = typename std::remove_pointer<decltype(ot)>::type;
+    const auto go = [&](auto* ct) {
+      using TC = typename std::remove_pointer<decltype(ct)>::type;
+      if constexpr (std::is_same<TC, TO>::value) return (int)kBadArgument;  // (bk_cast has no such pair either)
+      else return launch_axis(xt, rows, cols, ld, axis, ot, scale, (double*)ws, stream, CastOut<TC>{ct});
+    };
+    switch (cast_dtype) {
+      case kF32: return go((float*)cast_out);
+      case kF64: return go((double*)cast_out);
+      case kBF16: return go((uint16_t*)cast_out);
+    }
+    return (int)kBadArgument;
+  });
+}
+
+BK_API int bk_reduce_axis_tail(int op, int dtype, const void* x, int64_t rows, int64_t cols, int64_t ld, int axis,
+                               void* out, void* ws, int tail_op, const void* tail_a, const void* tail_b, int64_t tail_n,
+                               void* tail_ws, void* tail_out, hipStream_t stream) {
+  if (!axis_args_ok(op, x, rows, cols, ld, axis, out, ws) || tail_a == x || tail_b == x) return kBadArgument;
+  const double scale = axis_scale(op, rows, cols, axis);
+  return dispatch_axis_dtype(dtype, x, out, [&](auto* xt, auto* ot) {
+    using TO = typename std::remove_pointer<decltype(ot)>::type;
+    Tail t;
+    if (!make_tail<TO>(tail_op, tail_a, tail_b, tail_n, tail_ws, tail_out, out, axis == 0 ? cols : rows, &t))
+      return (int)kBadArgument;
+    return dispatch_op<kRedCount>(tail_op, [&](auto opc) {
+      return launch_axis(xt, rows, cols, ld, axis, ot, scale, (double*)ws, stream, TailOut<decltype(opc)::value>{t});
+    });
+  });
 }
