@@ -5,7 +5,8 @@ Exposed to sandboxed code as the top-level module ``beekern`` (see
 (square & friends), deterministic reductions (sum, fused square-sum, dot,
 min/max), boolean masks (comparisons, fused counts, where, x[mask]), order statistics and
 histograms (median / percentile / quantile by radix select, np.histogram), 2-D broadcasting and
-per-axis max / min / var / std, bf16 MFMA GEMM and f64 / f32 MFMA GEMM at numpy's precision — source in ``csrc/kernels``.
+per-axis max / min / var / std, int64 arrays and the integer-valued draws (integers, poisson, binomial,
+geometric), bf16 MFMA GEMM and f64 / f32 MFMA GEMM at numpy's precision — source in ``csrc/kernels``.
 """
 
 from ._native import BeekernError, QuotaExceeded, library_path  # noqa: F401
@@ -31,6 +32,7 @@ from .array import (  # noqa: F401
     empty_cache,
     equal,
     exp,
+    floor_divide,
     from_numpy,
     from_torch,
     full,
@@ -55,6 +57,7 @@ from .array import (  # noqa: F401
     median,
     memory_stats,
     minimum,
+    mod,
     multiply,
     negative,
     normalize_dtype,
@@ -65,6 +68,7 @@ from .array import (  # noqa: F401
     quantile,
     random,
     relu,
+    remainder,
     set_lazy_random,
     set_quota,
     sigmoid,
@@ -87,3 +91,4 @@ float32 = "float32"
 float64 = "float64"
 bfloat16 = "bfloat16"
 bool_ = "bool"
+int64 = "int64"

@@ -102,6 +102,11 @@ SIGNATURES = {
     "bk_fill": ([c_vp, c_i64, c_u64, c_int, c_vp], c_int),
     "bk_reduce": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp], c_int),
     "bk_rand_reduce": ([c_int, c_int, c_i64, c_u64, c_u64, c_d, c_d, c_vp, c_vp, c_vp], c_int),
+    "bk_int_binary": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp], c_int),
+    "bk_int_compare": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp], c_int),
+    "bk_int_reduce": ([c_int, c_vp, c_i64, c_vp, c_vp, c_vp], c_int),
+    "bk_int_cast": ([c_int, c_int, c_vp, c_vp, c_i64, c_vp], c_int),
+    "bk_rand_int": ([c_int, c_vp, c_i64, c_u64, c_u64, c_i64, c_i64, c_d, c_vp], c_int),
     "bk_compare": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_vp, c_i64, c_vp], c_int),
     "bk_compare_count": ([c_int, c_int, c_int, c_vp, c_vp, c_d, c_i64, c_vp, c_vp, c_vp], c_int),
     "bk_mask_logical": ([c_int, c_vp, c_vp, c_vp, c_i64, c_vp], c_int),

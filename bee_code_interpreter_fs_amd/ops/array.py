@@ -45,7 +45,8 @@ from typing import Any, Optional, Sequence, Tuple
 from ._lazy import is_integer, is_number, np, numpy_loaded, scalar
 from ._native import DTYPE_CODES, DTYPE_SIZES, BeekernError, QuotaExceeded  # noqa: F401
 from .driver import (DIST_BETA, DIST_CAUCHY, DIST_EXPONENTIAL, DIST_GAMMA, DIST_GUMBEL, DIST_LAPLACE, DIST_LOGISTIC,
-                     DIST_LOGNORMAL, DIST_PARETO, DIST_RAYLEIGH, DIST_STUDENT_T, DIST_WEIBULL, make_driver)
+                     DIST_LOGNORMAL, DIST_PARETO, DIST_RAYLEIGH, DIST_STUDENT_T, DIST_WEIBULL, RINT_BINOMIAL,
+                     RINT_GEOMETRIC, RINT_INTEGERS, RINT_POISSON, make_driver)
 
 Shape = Tuple[int, ...]
 
@@ -59,8 +60,12 @@ _REDUCE = {"sum": 0, "square_sum": 1, "abs_sum": 2, "max": 3, "min": 4, "dot": 5
 _COMPARE = {"less": 0, "less_equal": 1, "greater": 2, "greater_equal": 3, "equal": 4, "not_equal": 5}
 _FLIPPED = {0: 2, 1: 3, 2: 0, 3: 1, 4: 4, 5: 5}  # s OP x  ==  x FLIPPED[OP] s
 _LOGICAL = {"logical_and": 0, "logical_or": 1, "logical_xor": 2, "logical_not": 3}
-_SUPPORTED = ("float32", "float64", "bfloat16", "bool")
+_SUPPORTED = ("float32", "float64", "bfloat16", "bool", "int64")
 _FLOATS = ("float32", "float64", "bfloat16")
+# int64 arrays (csrc/kernels/integer.hip): op codes of bk_int_binary / bk_int_reduce
+_INT_BINARY = {"add": 0, "subtract": 1, "multiply": 2, "floor_divide": 3, "remainder": 4, "maximum": 5, "minimum": 6}
+_INT_REDUCE = {"sum": 0, "max": 1, "min": 2}
+_I64_MIN, _I64_MAX = -(1 << 63), (1 << 63) - 1
 
 _state_lock = threading.Lock()
 _driver = None
@@ -281,6 +286,7 @@ class DeviceArray:
 
     @property
     def T(self) -> "DeviceArray":
+        _no_int64("T", self)
         if self.ndim != 2:
             raise ValueError("T needs a 2-D array")
         self._materialize()
@@ -290,6 +296,8 @@ class DeviceArray:
         dt = normalize_dtype(dtype)
         if dt == self.dtype:
             return self.copy()
+        if "int64" in (dt, self.dtype):
+            return _int_astype(self, dt)
         if "bool" in (dt, self.dtype):
             if dt not in ("float32", "float64"):
                 raise TypeError(f"beekern astype: {self.dtype} -> {dt} has no kernel (bool converts to float32 / float64)")
@@ -303,8 +311,8 @@ class DeviceArray:
         return out
 
     def copy(self) -> "DeviceArray":
-        if self.dtype == "bool":
-            out = DeviceArray(self.shape, "bool")
+        if self.dtype in ("bool", "int64"):
+            out = DeviceArray(self.shape, self.dtype)
             driver().copy(out.ptr, self.ptr, self.nbytes)
             return out
         return _unary("copy", self)
@@ -325,7 +333,8 @@ class DeviceArray:
         count = count_nonzero(key)  # (a lazy mask: the fused count)
         out = DeviceArray((count,), self.dtype)
         if count:
-            driver().compress(self.code, self.ptr, key.ptr, self.size, out.ptr, count)
+            # (int64 elements move by size, as float64's)
+            driver().compress(_bits_code(self), self.ptr, key.ptr, self.size, out.ptr, count)
         return out
 
     def sum(self, axis: Optional[int] = None, keepdims: bool = False):
@@ -335,12 +344,12 @@ class DeviceArray:
         return mean(self, axis, keepdims)
 
     def max(self, axis: Optional[int] = None, keepdims: bool = False):
-        if axis is None and not keepdims:
+        if axis is None and not keepdims and self.dtype != "int64":
             return _reduce("max", self)
         return amax(self, axis, keepdims)
 
     def min(self, axis: Optional[int] = None, keepdims: bool = False):
-        if axis is None and not keepdims:
+        if axis is None and not keepdims and self.dtype != "int64":
             return _reduce("min", self)
         return amin(self, axis, keepdims)
 
@@ -355,13 +364,18 @@ class DeviceArray:
     def __sub__(self, o): return _binary("subtract", self, o)
     def __rsub__(self, o): return _binary("subtract", self, o, reversed_=True)
     def __mul__(self, o):
-        if o is self:
+        if o is self and self.dtype != "int64":
             return square(self)
         return _binary("multiply", self, o)
     def __rmul__(self, o): return _binary("multiply", self, o)
     def __truediv__(self, o): return _binary("divide", self, o)
     def __rtruediv__(self, o): return _binary("divide", self, o, reversed_=True)
+    def __floordiv__(self, o): return floor_divide(self, o)
+    def __rfloordiv__(self, o): return floor_divide(o, self)
+    def __mod__(self, o): return remainder(self, o)
+    def __rmod__(self, o): return remainder(o, self)
     def __pow__(self, o):
+        _no_int64("power", self)
         if isinstance(o, (int, float)) and o == 2:
             return square(self)
         return _binary("power", self, o)
@@ -399,7 +413,7 @@ def _binding():
 
 
 def _np_dtype(dtype: str):
-    return {"float32": np.float32, "float64": np.float64, "bool": np.bool_}[dtype]
+    return {"float32": np.float32, "float64": np.float64, "bool": np.bool_, "int64": np.int64}[dtype]
 
 
 def _np_view_dtype(dtype: str):
@@ -454,6 +468,8 @@ def full(shape, value: float, dtype="float64") -> DeviceArray:
     # the fill's bit pattern (no numpy: see ops/_lazy.py)
     if a.dtype == "bool":
         pattern, width = (1 if value else 0), 1
+    elif a.dtype == "int64":
+        pattern, width = _int64_scalar(value if is_integer(value) else int(value)) & 0xFFFFFFFFFFFFFFFF, 8
     elif a.dtype == "float64":
         pattern, width = struct.unpack("<Q", struct.pack("<d", float(value)))[0], 8
     elif a.dtype == "float32":
@@ -478,6 +494,7 @@ def asarray(obj, dtype=None) -> DeviceArray:
     if _is_torch_tensor(obj):
         return from_torch(obj) if dtype is None else from_torch(obj).astype(dtype)
     host = np.asarray(obj)
+    # (integer host data becomes float64 unless int64 is asked for)
     dt = normalize_dtype(dtype if dtype is not None else (host.dtype if host.dtype.kind == "f" else "float64"))
     if dt == "bfloat16":
         buf = _upload(_f32_to_bf16_bits(host.astype(np.float32)), "bfloat16")
@@ -532,6 +549,8 @@ def _no_masks(what: str, *arrays) -> None:
 
 def _unary(op: str, x) -> DeviceArray:
     x = _as_operand(x)
+    if x.dtype == "int64":
+        return _int_unary(op, x)
     _no_masks(op, x)
     x._materialize()
     out = DeviceArray(x.shape, x.dtype)
@@ -544,6 +563,8 @@ def square(x) -> DeviceArray:
     still-lazy uniform draw stays lazy underneath (sum(square(rand)) is one
     fused Philox->square->reduce kernel)."""
     x = _as_operand(x)
+    if x.dtype == "int64":
+        return _int_binary("multiply", x, x, False)
     if not _lazy_uniform(x):
         x = x._materialize()
     return DeviceArray(x.shape, x.dtype, lazy=("square", x))
@@ -620,6 +641,8 @@ def _binary_unequal(op: str, a: DeviceArray, b: DeviceArray, reversed_: bool) ->
 
 
 def _binary(op: str, a, b, reversed_: bool = False) -> DeviceArray:
+    if _is_int64(a) or _is_int64(b):
+        return _int_binary(op, a, b, reversed_)
     a = _as_operand(a)
     _no_masks(op, a)
     if is_number(b):
@@ -695,6 +718,8 @@ def _kept(res, x: DeviceArray, axis: Optional[int]):
 
 def sum(x, axis: Optional[int] = None, keepdims: bool = False):  # noqa: A001 - numpy-compatible name
     x = _as_operand(x)
+    if x.dtype == "int64":
+        return _int_reduce("sum", x, axis, keepdims)
     if keepdims:
         if x.dtype == "bool":
             raise TypeError("beekern sum: keepdims of a bool array's count has no kernel")
@@ -725,7 +750,13 @@ def square_sum(x) -> np.float64:
 
 
 def mean(x, axis: Optional[int] = None, keepdims: bool = False):
+    """np.mean.  Of an int64 array: the exact (int64) sum divided once by the size, as a float64."""
     x = _as_operand(x)
+    if x.dtype == "int64":
+        if x.size == 0:
+            _int_reduce("sum", x, axis, keepdims)
+            return scalar(float("nan"))
+        return scalar(float(_int_reduce("sum", x, axis, keepdims)) / x.size)
     if keepdims:
         if x.dtype == "bool":
             raise TypeError("beekern mean: keepdims of a bool array's mean has no kernel")
@@ -741,6 +772,7 @@ def mean(x, axis: Optional[int] = None, keepdims: bool = False):
 
 def dot(a, b):
     a, b = _as_operand(a), _as_operand(b)
+    _no_int64("dot", a, b)
     if a.ndim == 2 or b.ndim == 2:
         return matmul(a, b)  # (.T views stay views: the GEMMs read them in place)
     a, b = a._materialize(), b._materialize()
@@ -812,6 +844,8 @@ def _axis_stat(what: str, x: DeviceArray, axis: int, ddof=0) -> DeviceArray:
 
 def _extremum(what: str, x, axis, keepdims: bool):
     x = _as_operand(x)
+    if x.dtype == "int64":
+        return _int_reduce(what, x, axis, keepdims)
     ax = _stat_axis(what, x, axis)
     if ax is None:
         res = _reduce(what, x._materialize())
@@ -887,6 +921,192 @@ def minimum(a, b): return _binary("minimum", a, b)
 def power(a, b): return _binary("power", a, b)
 
 
+def floor_divide(a, b):
+    """``a // b`` of int64 operands (Python's floor; 0 for a zero divisor, as numpy)."""
+    return _int_binary("floor_divide", a, b, False)
+
+
+def remainder(a, b):
+    """``a % b`` of int64 operands (the divisor's sign; 0 for a zero divisor, as numpy)."""
+    return _int_binary("remainder", a, b, False)
+
+
+mod = remainder
+
+
+# ---- int64 arrays (csrc/kernels/integer.hip) --------------------------------------------
+#
+# + - * // % maximum minimum, unary - and abs give int64 between int64 arrays of
+# one shape and with integer scalars that fit int64 (OverflowError otherwise, as
+# numpy 2).  A float scalar or a float32 / float64 array on the other side casts
+# the int64 side (and a float32 array: numpy's result is float64) to float64
+# and the float kernel runs; / always does.  Comparisons give ordinary bool
+# masks.  No broadcasting, .T, axis reductions, ** or matmul.
+
+def _is_int64(x) -> bool:
+    return isinstance(x, DeviceArray) and x.dtype == "int64"
+
+
+def _no_int64(what: str, *arrays) -> None:
+    for a in arrays:
+        if _is_int64(a):
+            raise TypeError(f"beekern {what}: no kernel for int64 arrays")
+
+
+def _bits_code(x: DeviceArray) -> int:
+    """The dtype code the kernels that move elements by size (compress, where) take for x."""
+    return DTYPE_CODES["float64"] if x.dtype == "int64" else x.code
+
+
+def _int64_scalar(v) -> int:
+    v = int(v)
+    if not _I64_MIN <= v <= _I64_MAX:
+        raise OverflowError(f"Python integer {v} out of bounds for int64")
+    return v
+
+
+def _is_int_scalar(v) -> bool:
+    return is_integer(v) or (numpy_loaded() is not None and isinstance(v, np.bool_))
+
+
+def _is_float_scalar(v) -> bool:
+    return is_number(v) and not is_integer(v)
+
+
+def _int_astype(x: DeviceArray, dt: str) -> DeviceArray:
+    """int64 <-> float32 / float64 / bool (bk_int_cast; to bool: ``x != 0``)."""
+    if "bfloat16" in (dt, x.dtype):
+        raise TypeError(f"beekern astype: {x.dtype} -> {dt} has no kernel (int64 converts to and from float32 / "
+                        "float64 / bool)")
+    if dt == "bool":
+        return _int_compare(_COMPARE["not_equal"], x, 0)
+    out = DeviceArray(x.shape, dt)
+    driver().int_cast(x.code, out.code, x.ptr, out.ptr, x.size)
+    return out
+
+
+def _as_float64(v):
+    """An operand of a mixed int64 / float operation as float64: arrays cast, scalars float()."""
+    if isinstance(v, DeviceArray):
+        if v.dtype not in ("int64", "float32", "float64"):
+            raise TypeError(f"beekern: no kernel for int64 with {v.dtype} arrays")
+        return v if v.dtype == "float64" else v.astype("float64")
+    return float(v)
+
+
+def _int_operand(what: str, v):
+    """An operand of an int64 operation: an int64 DeviceArray or an int that fits, or None if it is a float
+    operand (a float scalar, a float32 / float64 array or host data of floats)."""
+    if isinstance(v, DeviceArray):
+        if v.dtype == "int64":
+            return v
+        if v.dtype in ("float32", "float64"):
+            return None
+        raise TypeError(f"beekern {what}: no kernel for int64 with {v.dtype} arrays")
+    if _is_int_scalar(v):
+        return _int64_scalar(v)
+    if _is_float_scalar(v):
+        return None
+    host = np.asarray(v)
+    if host.dtype.kind in "iub":
+        return asarray(host, "int64")
+    if host.dtype.kind == "f":
+        return None
+    raise TypeError(f"beekern {what}: cannot combine an int64 DeviceArray with {type(v).__name__}")
+
+
+def _same_shape(what: str, a: DeviceArray, b: DeviceArray) -> None:
+    if a.shape != b.shape:
+        raise TypeError(f"beekern {what}: int64 arrays do not broadcast ({a.shape} vs {b.shape})")
+
+
+def _int_binary(op: str, a, b, reversed_: bool) -> DeviceArray:
+    lhs, rhs = (b, a) if reversed_ else (a, b)
+    if not (_is_int64(lhs) or _is_int64(rhs)):
+        raise TypeError(f"beekern {op}: int64 arrays only")
+    if op == "power":
+        raise TypeError("beekern power: no kernel for int64 arrays")
+    il, ir = _int_operand(op, lhs), _int_operand(op, rhs)
+    if op == "divide" or il is None or ir is None:
+        if op not in _BINARY:
+            raise TypeError(f"beekern {op}: no kernel for int64 with float operands")
+        fl = _as_float64(lhs if isinstance(lhs, DeviceArray) or is_number(lhs) else asarray(lhs))
+        fr = _as_float64(rhs if isinstance(rhs, DeviceArray) or is_number(rhs) else asarray(rhs))
+        if isinstance(fl, DeviceArray):
+            if isinstance(fr, DeviceArray):
+                _same_shape(op, fl, fr)
+            return _binary(op, fl, fr)
+        return _binary(op, fr, fl, reversed_=True)
+    code = _INT_BINARY[op]
+    if isinstance(il, DeviceArray) and isinstance(ir, DeviceArray):
+        if ir.size == 1 and il.shape != ir.shape:
+            ir = int(ir.item())
+        elif il.size == 1 and il.shape != ir.shape:
+            il = int(il.item())
+        else:
+            _same_shape(op, il, ir)
+            out = DeviceArray(il.shape, "int64")
+            driver().int_binary(code, 0, il.ptr, ir.ptr, 0, out.ptr, il.size)
+            return out
+    arr, sc, mode = (il, ir, 1) if isinstance(il, DeviceArray) else (ir, il, 2)
+    out = DeviceArray(arr.shape, "int64")
+    driver().int_binary(code, mode, arr.ptr, 0, sc, out.ptr, arr.size)
+    return out
+
+
+def _int_unary(op: str, x: DeviceArray) -> DeviceArray:
+    if op == "negative":
+        return _int_binary("subtract", 0, x, False)
+    if op == "abs":  # (INT64_MIN stays, as numpy's)
+        return _int_binary("maximum", x, _int_binary("subtract", 0, x, False), False)
+    if op == "copy":
+        return x.copy()
+    raise TypeError(f"beekern {op}: no kernel for int64 arrays")
+
+
+def _const_mask(shape, value: bool) -> DeviceArray:
+    return full(shape, value, "bool")
+
+
+def _int_compare(code: int, a, b) -> DeviceArray:
+    """A comparison with an int64 array on one side at least (a is a DeviceArray): a materialised bool mask."""
+    if not _is_int64(a):  # a float array against an int64 one
+        return _compare_code(code, _as_float64(a), _as_float64(b))
+    if _is_int_scalar(b):
+        v = int(b)
+        if not _I64_MIN <= v <= _I64_MAX:  # numpy 2: the exact comparison
+            true = {0: v > 0, 1: v > 0, 2: v < 0, 3: v < 0, 4: False, 5: True}[code]
+            return _const_mask(a.shape, true)
+        out = DeviceArray(a.shape, "bool")
+        driver().int_compare(code, 1, a.ptr, 0, v, out.ptr, a.size)
+        return out
+    ib = _int_operand("compare", b)
+    if ib is None:
+        fb = _as_float64(b if isinstance(b, DeviceArray) or is_number(b) else asarray(b))
+        return _compare_code(code, _as_float64(a), fb)
+    _same_shape("compare", a, ib)
+    out = DeviceArray(a.shape, "bool")
+    driver().int_compare(code, 0, a.ptr, ib.ptr, 0, out.ptr, a.size)
+    return out
+
+
+def _compare_code(code: int, a, b) -> DeviceArray:
+    name = next(k for k, v in _COMPARE.items() if v == code)
+    return _compare(name, a, b)
+
+
+def _int_reduce(what: str, x: DeviceArray, axis=None, keepdims: bool = False):
+    """sum (wrapping, as numpy's) / max / min of a whole int64 array as ``np.int64``."""
+    x._materialize()
+    if keepdims or not (axis is None or (x.ndim == 1 and is_integer(axis) and int(axis) in (0, -1))):
+        raise TypeError(f"beekern {what}: no axis or keepdims reductions of int64 arrays")
+    if what != "sum" and x.size == 0:
+        raise ValueError(f"zero-size array to reduction operation {what} which has no identity")
+    v = driver().int_reduce(_INT_REDUCE[what], x.ptr, x.size)
+    m = numpy_loaded()  # (np.int64 when numpy is loaded, else the same value as an int: ops/_lazy.py)
+    return m.int64(v) if m is not None else v
+
+
 # ---- boolean masks -------------------------------------------------------------------
 
 def _is_numpy_scalar(s) -> bool:
@@ -932,6 +1152,8 @@ def _compare(op: str, a, b) -> DeviceArray:
         if not isinstance(b, DeviceArray):
             raise TypeError(f"beekern {op}: one operand must be a DeviceArray")
         a, b, code = b, a, _FLIPPED[code]  # scalar OP array: the flipped operator
+    if a.dtype == "int64" or _is_int64(b):
+        return _int_compare(code, a, b)
     if a.dtype not in _FLOATS:
         raise TypeError(f"beekern {op}: float arrays only, got {a.dtype}")
     if not (a._lazy is None and not a._transposed):
@@ -983,6 +1205,8 @@ def count_nonzero(x) -> int:
     """The number of true (non-zero) elements.  A lazy mask, or a float array
     (``x != 0``), is counted in one fused pass with no mask written."""
     x = _as_operand(x)
+    if x.dtype == "int64":
+        x = _int_compare(_COMPARE["not_equal"], x, 0)
     if x.dtype != "bool":
         x = _compare("not_equal", x, 0.0)
     if _is_lazy_mask(x):
@@ -1037,6 +1261,8 @@ def where(mask, a, b, dtype=None) -> DeviceArray:
     arrays' dtype, two scalars give float64 (or ``dtype``).  Array values are
     moved as bits (NaN payloads and -0.0 survive)."""
     mask = _mask_operand("where", mask)
+    if _is_int64(a) or _is_int64(b) or (dtype is not None and normalize_dtype(dtype) == "int64"):
+        return _int_where(mask, a, b)
     arrays = [v for v in (a, b) if isinstance(v, DeviceArray)]
     for v in (a, b):
         if not isinstance(v, DeviceArray) and not (is_number(v) or _is_numpy_scalar(v)):
@@ -1061,6 +1287,29 @@ def where(mask, a, b, dtype=None) -> DeviceArray:
     out = DeviceArray(mask.shape, dt)
     driver().where(DTYPE_CODES[dt], mask.ptr, flags, a.ptr if not flags & 1 else 0, b.ptr if not flags & 2 else 0,
                    float(a) if flags & 1 else 0.0, float(b) if flags & 2 else 0.0, out.ptr, mask.size)
+    return out
+
+
+def _int_where(mask: DeviceArray, a, b) -> DeviceArray:
+    """``where`` with an int64 side.  Two int64 operands (arrays of the mask's shape, integers that fit) give
+    int64: scalars become arrays (``full``) and the values move as bits through the float64 form of the
+    kernel.  A float operand casts the int64 side to float64, as numpy's result is."""
+    sides = []
+    for v in (a, b):
+        if not isinstance(v, DeviceArray) and not (is_number(v) or _is_numpy_scalar(v)):
+            raise TypeError(f"beekern where: operands are DeviceArrays or numbers, got {type(v).__name__}")
+        sides.append(_int_operand("where", v))
+    if sides[0] is None or sides[1] is None:
+        return where(mask, _as_float64(a), _as_float64(b))
+    arrays = []
+    for v in sides:
+        if not isinstance(v, DeviceArray):
+            v = full(mask.shape, v, "int64")
+        if v.shape != mask.shape:
+            raise ValueError(f"beekern where: shapes must match the mask's ({v.shape} vs {mask.shape})")
+        arrays.append(v)
+    out = DeviceArray(mask.shape, "int64")
+    driver().where(DTYPE_CODES["float64"], mask.ptr, 0, arrays[0].ptr, arrays[1].ptr, 0.0, 0.0, out.ptr, mask.size)
     return out
 
 
@@ -1312,6 +1561,7 @@ def matmul(a, b, out_dtype: Optional[str] = None) -> DeviceArray:
     """
     a = _as_operand(a)
     b = _as_operand(b)
+    _no_int64("matmul", a, b)
     if out_dtype is None:
         if _fp_dtype(a) and _fp_dtype(b):
             return matmul_fp(a, b)
@@ -1499,6 +1749,65 @@ class Generator:
     def standard_t(self, df, size=None, dtype="float64") -> DeviceArray:
         return self._dist(DIST_STUDENT_T, _param("df", df, 1), 0.0, size, dtype, per=1)
 
+    # ---- the integer-valued draws of bk_rand_int (csrc/kernels/integer.hip): int64, numpy's names and defaults ----
+    def _rint(self, kind: int, a: int, b: int, p: float, size, per: int) -> DeviceArray:
+        """A draw of ``kind``.  per: elements a counter yields (1: a substream each)."""
+        shape = _shape_of(size)
+        n = int(math.prod(shape)) if shape else 1
+        off = self._advance(n, per)
+        out = DeviceArray(shape, "int64")
+        driver().rand_int(kind, out.ptr, out.size, self._seed, off, a, b, float(p))
+        return out
+
+    def integers(self, low, high=None, size=None, endpoint: bool = False) -> DeviceArray:
+        """Uniform integers of [low, high) ([0, low) without ``high``; ``endpoint``: [low, high])."""
+        if high is None:
+            low, high = 0, low
+        low, high = _int_param("low", low), _int_param("high", high)
+        if endpoint:
+            high += 1
+        if not low < high <= _I64_MAX:
+            raise ValueError("low >= high" if low >= high else "high is out of bounds for int64")
+        return self._rint(RINT_INTEGERS, low, high, 0.0, size, 4 if high - low <= (1 << 32) else 2)
+
+    def randint(self, low, high=None, size=None) -> DeviceArray:
+        return self.integers(low, high, size)
+
+    def poisson(self, lam=1.0, size=None) -> DeviceArray:
+        lam = _param("lam", lam, 0)
+        if lam > 9007199254740992.0:
+            raise ValueError("lam value too large")
+        return self._rint(RINT_POISSON, 0, 0, lam, size, 1)
+
+    def binomial(self, n, p, size=None) -> DeviceArray:
+        n, p = _int_param("n", n), _param("p", p)
+        if n < 0:
+            raise ValueError("n < 0")
+        if n >= 1 << 53:
+            raise ValueError("n too large")
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("p < 0, p > 1 or p is NaN")
+        return self._rint(RINT_BINOMIAL, n, 0, p, size, 1)
+
+    def geometric(self, p, size=None) -> DeviceArray:
+        p = _param("p", p)
+        if not 0.0 < p <= 1.0:
+            raise ValueError("p <= 0, p > 1 or p contains NaNs")
+        return self._rint(RINT_GEOMETRIC, 0, 0, p, size, 2)
+
+
+def _int_param(name: str, v) -> int:
+    """An integer parameter of a draw that fits int64 (ValueError otherwise)."""
+    if not is_integer(v):
+        f = float(v)
+        if not math.isfinite(f) or f != math.floor(f):
+            raise ValueError(f"{name} must be an integer")
+        v = int(f)
+    v = int(v)
+    if not _I64_MIN <= v <= _I64_MAX:
+        raise ValueError(f"{name} is out of bounds for int64")
+    return v
+
 
 def _param(name: str, v, rule: int = -1) -> float:
     """A distribution's parameter as a finite float; rule 0: >= 0, 1: > 0 (ValueError in numpy's words)."""
@@ -1561,6 +1870,14 @@ class _RandomModule:
     def chisquare(self, df, size=None, dtype="float64"): return self.gen.chisquare(df, size, dtype)
     def beta(self, a, b, size=None, dtype="float64"): return self.gen.beta(a, b, size, dtype)
     def standard_t(self, df, size=None, dtype="float64"): return self.gen.standard_t(df, size, dtype)
+
+    def integers(self, low, high=None, size=None, endpoint=False):
+        return self.gen.integers(low, high, size, endpoint)
+
+    def randint(self, low, high=None, size=None): return self.gen.randint(low, high, size)
+    def poisson(self, lam=1.0, size=None): return self.gen.poisson(lam, size)
+    def binomial(self, n, p, size=None): return self.gen.binomial(n, p, size)
+    def geometric(self, p, size=None): return self.gen.geometric(p, size)
 
 
 random = _RandomModule()

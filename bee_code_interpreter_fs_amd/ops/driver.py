@@ -46,6 +46,9 @@ WS_REDUCE, WS_REDUCE_AXIS, WS_AXIS_STAT, WS_COMPRESS, WS_SELECT, WS_HISTOGRAM, W
 (DIST_EXPONENTIAL, DIST_LAPLACE, DIST_LOGISTIC, DIST_GUMBEL, DIST_RAYLEIGH, DIST_WEIBULL, DIST_PARETO, DIST_CAUCHY,
  DIST_LOGNORMAL, DIST_GAMMA, DIST_BETA, DIST_STUDENT_T, DIST_COUNT) = range(13)
 
+# the integer-valued draws of bk_rand_int: enum BkRandInt of csrc/kernels/beekern.h
+RINT_INTEGERS, RINT_POISSON, RINT_BINOMIAL, RINT_GEOMETRIC, RINT_COUNT = range(5)
+
 
 class NativeDriver:
     name = "native"
@@ -194,6 +197,33 @@ class NativeDriver:
         check(self.lib.bk_compress(dt, _vp(x), _vp(mask), n, _vp(y), cap, _vp(self._workspace(WS_COMPRESS)), self.stream),
               "bk_compress")
 
+    # ---- int64 arrays (csrc/kernels/integer.hip) ---------------------------------------
+    def rand_int(self, kind: int, h: int, n: int, seed: int, off: int, a: int, b: int, p: float) -> None:
+        """n int64 draws of ``kind`` (a RINT_* code) into h; a, b, p: the kind's parameters."""
+        check(self.lib.bk_rand_int(kind, _vp(h), n, seed, off, int(a), int(b), float(p), self.stream), "bk_rand_int")
+
+    def int_binary(self, op: int, mode: int, a: int, b: int, sc: int, y: int, n: int) -> None:
+        """y = a OP (b | sc) on int64; op 0 + 1 - 2 * 3 // 4 % 5 max 6 min; mode as ``binary``; y may be a or b."""
+        check(self.lib.bk_int_binary(op, mode, _vp(a), _vp(b) if b else None, int(sc), _vp(y), n, self.stream),
+              "bk_int_binary")
+
+    def int_compare(self, op: int, mode: int, a: int, b: int, sc: int, y: int, n: int) -> None:
+        """y[i] = a[i] OP (b[i] | sc) as 0 / 1 bytes; the op codes of ``compare``; mode 0 array, 1 scalar."""
+        check(self.lib.bk_int_compare(op, mode, _vp(a), _vp(b) if b else None, int(sc), _vp(y), n, self.stream),
+              "bk_int_compare")
+
+    def int_reduce(self, op: int, a: int, n: int) -> int:
+        """op 0 sum (wrapping), 1 max, 2 min of n int64, as a Python int."""
+        check(self.lib.bk_int_reduce(op, _vp(a), n, _vp(self.workspaces[WS_REDUCE]), _vp(self.scalar), self.stream),
+              "bk_int_reduce")
+        out = np.zeros(1, np.int64)
+        self.d2h(self.scalar, out)
+        return int(out[0])
+
+    def int_cast(self, s: int, d: int, x: int, y: int, n: int) -> None:
+        """int64 -> f64 / f32, f64 / f32 / bool -> int64 (dtype codes)."""
+        check(self.lib.bk_int_cast(s, d, _vp(x), _vp(y), n, self.stream), "bk_int_cast")
+
     # ---- order statistics and histograms (csrc/kernels/stats.hip) ---------------------
     def _stats_scratch(self) -> int:
         """Device scratch of the two ops: 33 f64 select results, then the
@@ -289,7 +319,8 @@ def _info_dict(v, arch: str) -> dict:
 
 (HELLO, ALLOC, FREE, WRITE, READ, RAND, UNARY, BINARY, CAST, FILL, REDUCE, GEMM, TRANSPOSE, SYNC, MEMSTATS, INFO,
  COPY, RAND_REDUCE, ALLOC_AT, REDUCE_AXIS, GEMM_FP, COMPARE, COMPARE_COUNT, MASK_LOGICAL, WHERE,
- COMPRESS, SELECT, HISTOGRAM, BROADCAST, AXIS_STAT, RAND_DIST) = range(1, 32)
+ COMPRESS, SELECT, HISTOGRAM, BROADCAST, AXIS_STAT, RAND_DIST, RAND_INT, INT_BINARY, INT_COMPARE, INT_REDUCE,
+ INT_CAST) = range(1, 37)
 _HDR = struct.Struct("<IIQ")
 _NO_REPLY = 1  # request flag: no response unless a later request collects an error
 _RHDR = struct.Struct("<iIQ")
@@ -557,6 +588,23 @@ class BrokerDriver:
 
     def compress(self, dt, x, mask, n, y, cap) -> None:
         self._post(COMPRESS, struct.pack("<IIQQqQq", dt, 0, x, mask, n, y, cap))
+
+    # int64 arrays: payload layouts beside the op enum in csrc/executor/broker_core.hpp
+    def rand_int(self, kind, h, n, seed, off, a, b, p) -> None:
+        self._post(RAND_INT, struct.pack("<IIQqQQqqd", kind, 0, h, n, seed & 0xFFFFFFFFFFFFFFFF, off, int(a), int(b),
+                                         float(p)))
+
+    def int_binary(self, op, mode, a, b, sc, y, n) -> None:
+        self._post(INT_BINARY, struct.pack("<IIQQqQq", op, mode, a, b or 0, int(sc), y, n))
+
+    def int_compare(self, op, mode, a, b, sc, y, n) -> None:
+        self._post(INT_COMPARE, struct.pack("<IIQQqQq", op, mode, a, b or 0, int(sc), y, n))
+
+    def int_reduce(self, op, a, n) -> int:
+        return struct.unpack("<q", self._call(INT_REDUCE, struct.pack("<IIQq", op, 0, a, n)))[0]
+
+    def int_cast(self, s, d, x, y, n) -> None:
+        self._post(INT_CAST, struct.pack("<IIQQq", s, d, x, y, n))
 
     # order statistics and histograms: both reply, like REDUCE
     def select(self, dt, x, n, ranks) -> tuple:

@@ -54,6 +54,16 @@ what numpy would (same dtype rules, same shape):
   (``BEE_NUMPY_OFFLOAD_MATMUL=bf16`` rounds f32 / f64 products to the bf16
   GEMM instead, as before).
 
+* on ``int64`` arrays (``csrc/kernels/integer.hip``): ``add`` / ``subtract`` /
+  ``multiply`` / ``floor_divide`` / ``remainder`` (``mod``) / ``true_divide`` /
+  ``maximum`` / ``minimum`` / ``negative`` / ``absolute`` and the six
+  comparisons, with an int64 array of the same shape, an integer scalar that
+  fits (int64 results) or a float scalar / f32 / f64 array (float64 results,
+  as numpy's); ``sum`` / ``max`` / ``min`` (``np.int64``), ``mean``
+  (``np.float64``) and ``count_nonzero`` of a whole array; ``where(mask, a,
+  b)``.  Keyword forms (``out=``, ``dtype=``, ``axis=``) and every other
+  function of an int64 array go to the host.
+
 Everything else copies the operands to the host (``__array__``) and runs
 numpy there, with one ``HostFallbackWarning`` per function per process
 (``BEE_OFFLOAD_WARN=0`` silences it).  ``np.sum(device_array)`` used to
@@ -138,6 +148,8 @@ def _as_result_scalar(v, dtype_name: str):
         if isinstance(v, (bool, np.bool_)):
             return np.bool_(v)
         return np.int64(v) if isinstance(v, (int, np.integer)) else np.float64(v)
+    if dtype_name == "int64":  # sum / max / min are int64, a mean float64
+        return np.int64(v) if isinstance(v, (int, np.integer)) else np.float64(v)
     if dtype_name == "float32":
         return np.float32(v)
     return np.float64(v)
@@ -182,6 +194,8 @@ def _matmul(b: Binding, A, x, y, name: str = "matmul"):
         return None
     if (dx is None and b.is_mine(x)) or (dy is None and b.is_mine(y)):
         return None  # a host-resident offload array: everything stays on the host
+    if "int64" in (getattr(dx, "dtype", None), getattr(dy, "dtype", None)):
+        return None  # (no integer product on the device)
     if "bfloat16" in (getattr(dx, "dtype", None), getattr(dy, "dtype", None)):
         if dx is None or dy is None or dx.dtype != dy.dtype or dx.ndim != 2 or dy.ndim != 2 or \
                 dx.shape[1] != dy.shape[0]:
@@ -251,6 +265,8 @@ def _try_ufunc(b, A, ufunc, name, method, inputs, kwargs, extra) -> Optional[Any
         arrays = [d for d in devs if d is not None]
         if not arrays or any(b.is_mine(x) and d is None for x, d in zip(inputs, devs)):
             return None  # a host-resident operand: everything stays on the host
+        if any(d.dtype == "int64" for d in arrays):
+            return None if (out is not None or extra) else _try_int_ufunc(A, name, inputs, devs)
         dt = arrays[0].dtype
         if kwargs.get("dtype") is not None and np.dtype(kwargs["dtype"]).name != dt:
             return None
@@ -296,6 +312,8 @@ def _try_ufunc(b, A, ufunc, name, method, inputs, kwargs, extra) -> Optional[Any
         axis = kwargs.get("axis", 0)
         if axis is None or (x.ndim == 1 and axis in (0, -1)):
             return _full_reduce(A, _REDUCE[name], x)
+        if x.dtype == "int64":
+            return None  # (no axis reductions of int64 arrays)
         if x.ndim == 2 and _is_axis(axis, (0, 1, -1, -2)):
             if name == "add":
                 return A.sum(x, axis=axis)
@@ -303,6 +321,61 @@ def _try_ufunc(b, A, ufunc, name, method, inputs, kwargs, extra) -> Optional[Any
                 return _axis_result(lambda: A.amax(x, axis) if name == "maximum" else A.amin(x, axis))
         return None
     return None
+
+
+_INT_BINARY = {"add": "add", "subtract": "subtract", "multiply": "multiply", "floor_divide": "floor_divide",
+               "remainder": "remainder", "mod": "remainder", "true_divide": "divide", "divide": "divide",
+               "maximum": "maximum", "minimum": "minimum"}
+_INT_UNARY = {"negative": "negative", "absolute": "abs"}
+_INT_FUNCTIONS = ("sum", "mean", "max", "min", "amax", "amin", "count_nonzero")
+_ANY_DTYPE_FUNCTIONS = ("shape", "ndim", "size", "copy", "reshape", "ravel")
+
+
+def _try_int_ufunc(A, name, inputs, devs) -> Optional[Any]:
+    """A ufunc with an int64 device array among its inputs (no ``out=``, no keywords): the device result
+    under the rules of ``ops/array.py``'s int64 section, or None for a host fallback.  An integer scalar that
+    does not fit int64 raises OverflowError, as numpy 2 does."""
+    operands = []
+    for x, d in zip(inputs, devs):
+        if d is not None:
+            if d.dtype not in ("int64", "float32", "float64"):
+                return None
+            operands.append(d)
+        elif isinstance(x, (bool, int, float, np.floating, np.integer, np.bool_)) and getattr(x, "itemsize", 8) <= 8:
+            operands.append(x)
+        else:
+            return None  # (a host array or something else: numpy decides)
+    try:
+        if name in _INT_UNARY and len(operands) == 1:
+            return A._unary(_INT_UNARY[name], operands[0])
+        if len(operands) != 2:
+            return None
+        x, y = operands
+        if isinstance(x, A.DeviceArray) and isinstance(y, A.DeviceArray) and x.shape != y.shape:
+            return None
+        if name in _INT_BINARY:
+            return A._int_binary(_INT_BINARY[name], x, y, False)
+        if name in _COMPARE:
+            return A._compare(name, x, y)
+    except (TypeError, ValueError):
+        return None
+    return None
+
+
+def _try_int_function(b, A, name, args, kwargs, x):
+    """A numpy function whose first argument is the int64 device array ``x``: sum / max / min / mean /
+    count_nonzero of the whole array, or _NO."""
+    if name not in _INT_FUNCTIONS:
+        return _NO
+    got = _bind(name, args, kwargs, ("a",))
+    if got is None or set(got) != {"a"}:
+        return _NO  # (axis=, dtype=, out=, keepdims=, ...: numpy's own answer)
+    if name == "count_nonzero":
+        return A.count_nonzero(x)
+    if name in ("max", "min", "amax", "amin") and x.size == 0:
+        return _NO
+    fn = {"sum": A.sum, "mean": A.mean, "max": A.amax, "amax": A.amax, "min": A.amin, "amin": A.amin}[name]
+    return _as_result_scalar(fn(x), "int64")
 
 
 def _is_axis(axis, allowed) -> bool:
@@ -487,6 +560,9 @@ def _try_histogram(b: Binding, A, args, kwargs):
 
 
 def _try_function(b, A, name, mod, args, kwargs):
+    first = b.dev(args[0]) if args else None
+    if first is not None and first.dtype == "int64" and name not in _ANY_DTYPE_FUNCTIONS:
+        return _try_int_function(b, A, name, args, kwargs, first)
     if name in ("shape", "ndim", "size") and args and b.dev(args[0]) is not None and len(args) + len(kwargs) == 1:
         d = b.dev(args[0])
         return {"shape": d.shape, "ndim": d.ndim, "size": d.size}[name]

@@ -56,6 +56,7 @@ class HipDevice final : public broker::Device {
   X(select) X(histogram)                                           /* order statistics, histograms (stats.hip) */    \
   X(broadcast) X(axis_stat)                                        /* matrix against vector, axis statistics (axis.hip) */ \
   X(rand_dist)                                                     /* continuous distributions (random.hip) */ \
+  X(rand_int) X(int_binary) X(int_compare) X(int_reduce) X(int_cast) /* int64 arrays (integer.hip) */                \
   X(reduce_axis_cast) X(reduce_axis_tail) X(gemm_bf16_tn_tail)     /* a producer with its cast or closing reduce */
   struct Bk {
 #define X(name) decltype(&bk_##name) name = nullptr;
@@ -585,6 +586,38 @@ class HipDevice final : public broker::Device {
       return bk.compare_count((int)op, (int)dt, (int)mode, a, b, sc, n, c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
     });
     return fetch(c, rc, out);
+  }
+  // int64 arrays (integer.hip)
+  int rand_int(uint32_t kind, void* y, int64_t n, uint64_t seed, uint64_t off, int64_t a, int64_t b, double p,
+               void* s) override {
+    return timed(s, st(s), [&](hipStream_t q) { return bk.rand_int((int)kind, y, n, seed, off, a, b, p, q); });
+  }
+  int int_binary(uint32_t op, uint32_t mode, const void* a, const void* b, int64_t sc, void* y, int64_t n,
+                 void* s) override {
+    return timed(s, st(s), [&](hipStream_t q) { return bk.int_binary((int)op, (int)mode, a, b, sc, y, n, q); });
+  }
+  int int_compare(uint32_t op, uint32_t mode, const void* a, const void* b, int64_t sc, void* y, int64_t n,
+                  void* s) override {
+    return timed(s, st(s), [&](hipStream_t q) { return bk.int_compare((int)op, (int)mode, a, b, sc, y, n, q); });
+  }
+  int int_reduce(uint32_t op, const void* a, int64_t n, int64_t* out, void* s) override {
+    Ctx* c = (Ctx*)s;
+    const int rc = timed(s, st(s), [&](hipStream_t q) {
+      return bk.int_reduce((int)op, a, n, c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
+    });
+    if (rc != 0) return rc;
+    // the result slot's 8 bytes as an int64 (fetch() reads them as a double)
+    if (c->slot == nullptr) {
+      if (hipMemcpyAsync(out, c->scalar, 8, hipMemcpyDeviceToHost, c->s) != hipSuccess || !wait(c))
+        return broker::kLaunchFailed;
+      return 0;
+    }
+    if (!wait(c)) return broker::kLaunchFailed;
+    *out = *(volatile int64_t*)c->slot;
+    return 0;
+  }
+  int int_cast(uint32_t sdt, uint32_t ddt, const void* x, void* y, int64_t n, void* s) override {
+    return timed(s, st(s), [&](hipStream_t q) { return bk.int_cast((int)sdt, (int)ddt, x, y, n, q); });
   }
   int mask_logical(uint32_t op, const void* a, const void* b, void* y, int64_t n, void* s) override {
     return timed(s, st(s),

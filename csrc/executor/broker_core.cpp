@@ -18,7 +18,8 @@ const char* op_name(uint32_t op) {
                                       "bk.memstats", "bk.info",  "bk.copy",   "bk.rand_reduce", "bk.alloc_at",
                                       "bk.reduce_axis", "bk.gemm_fp", "bk.compare", "bk.compare_count",
                                       "bk.mask_logical", "bk.where", "bk.compress", "bk.select", "bk.histogram",
-                                      "bk.broadcast", "bk.axis_stat", "bk.rand_dist"};
+                                      "bk.broadcast", "bk.axis_stat", "bk.rand_dist", "bk.rand_int", "bk.int_binary",
+                                      "bk.int_compare", "bk.int_reduce", "bk.int_cast"};
   return op < sizeof(names) / sizeof(names[0]) ? names[op] : names[0];
 }
 
@@ -226,6 +227,36 @@ Weight frame_weight(uint32_t op, const char* payload, uint64_t len) {
       r.get<uint32_t>(), r.get<uint64_t>();
       const int64_t n = r.get<int64_t>();
       return weigh(short_bytes(n, elem(dt)));
+    }
+    // the int64 ops, weighed as their float twins at 8 bytes an element
+    case kRandInt: {  // as kRand
+      r.get<uint32_t>(), r.get<uint32_t>(), r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      return weigh(short_bytes(n, 8));
+    }
+    case kIntBinary: {  // as kBinary
+      r.get<uint32_t>(), r.get<uint32_t>(), r.get<uint64_t>(), r.get<uint64_t>(), r.get<int64_t>(), r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      return weigh(short_bytes(n, 8, 3));
+    }
+    case kIntCompare: {  // as kCompare
+      r.get<uint32_t>();
+      const uint32_t mode = r.get<uint32_t>();
+      r.get<uint64_t>(), r.get<uint64_t>(), r.get<int64_t>(), r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      return weigh(short_bytes(n, 8 * (mode == 0 ? 2 : 1) + 1));
+    }
+    case kIntReduce: {  // as kReduce
+      r.get<uint32_t>(), r.get<uint32_t>(), r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      return weigh(short_bytes(n, 8));
+    }
+    case kIntCast: {  // as kCast
+      const uint32_t s = r.get<uint32_t>(), d = r.get<uint32_t>();
+      r.get<uint64_t>(), r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      const auto size = [](uint32_t dt) -> int64_t { return dt == 0 ? 4 : dt == kDtBool ? 1 : 8; };
+      return weigh(short_bytes(n, size(s) + size(d)));
     }
   }
   return kLong;  // an unknown op launches nothing; counted as long, it moves nothing to the priority lane
@@ -934,6 +965,88 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
         return kBadHandle;
       if (!will_read(bx) || !will_write(by, 0, ny)) return kLaunchFailed;
       return dev_.axis_stat(sop, dt, bx->ptr, by->ptr, rows, cols, ld, axis, divisor, stream_);
+    }
+    case kRandInt: {
+      const uint32_t kind = r.get<uint32_t>();
+      r.get<uint32_t>();
+      const uint64_t h = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      const uint64_t seed = r.get<uint64_t>(), off = r.get<uint64_t>();
+      const int64_t a = r.get<int64_t>(), bb = r.get<int64_t>();
+      const double p = r.get<double>();
+      if (!r.ok) return kProtocol;
+      // what the draw cannot take is refused here, before the device is asked
+      if (kind >= kRandIntCount || !rand_int_params_ok(kind, a, bb, p)) return kBadArgument;
+      uint64_t need;
+      Buf* b = lookup(h);
+      if (n < 0 || !mul_ok((uint64_t)n, 8, &need) || !b || need > b->size) return kBadHandle;
+      if (!will_write(b, 0, need)) return kLaunchFailed;
+      return dev_.rand_int(kind, b->ptr, n, seed, off, a, bb, p, stream_);
+    }
+    case kIntBinary: {
+      const uint32_t bop = r.get<uint32_t>(), mode = r.get<uint32_t>();
+      const uint64_t a = r.get<uint64_t>(), bh = r.get<uint64_t>();
+      const int64_t sc = r.get<int64_t>();
+      const uint64_t y = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      if (bop >= kIntBinaryCount || mode > 2) return kBadArgument;
+      uint64_t need;
+      Buf *ba = lookup(a), *bb = mode == 0 ? lookup(bh) : nullptr, *by = lookup(y);
+      if (n < 0 || !mul_ok((uint64_t)n, 8, &need) || !ba || !by || need > ba->size || need > by->size ||
+          (mode == 0 && (!bb || need > bb->size)))
+        return kBadHandle;
+      if (!will_read(ba) || !will_read(bb) || !will_write(by, 0, need)) return kLaunchFailed;
+      return dev_.int_binary(bop, mode, ba->ptr, bb ? bb->ptr : nullptr, sc, by->ptr, n, stream_);
+    }
+    case kIntCompare: {
+      const uint32_t cop = r.get<uint32_t>(), mode = r.get<uint32_t>();
+      const uint64_t a = r.get<uint64_t>(), bh = r.get<uint64_t>();
+      const int64_t sc = r.get<int64_t>();
+      const uint64_t y = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      if (cop > 5 || mode > 1) return kBadArgument;
+      uint64_t need;
+      Buf *ba = lookup(a), *bb = mode == 0 ? lookup(bh) : nullptr, *by = lookup(y);
+      // the mask is n bytes, written while other lanes still read a and b: its own buffer
+      if (n < 0 || !mul_ok((uint64_t)n, 8, &need) || !ba || need > ba->size || (mode == 0 && (!bb || need > bb->size)) ||
+          !by || (uint64_t)n > by->size || by == ba || by == bb)
+        return kBadHandle;
+      if (!will_read(ba) || !will_read(bb) || !will_write(by, 0, (uint64_t)n)) return kLaunchFailed;
+      return dev_.int_compare(cop, mode, ba->ptr, bb ? bb->ptr : nullptr, sc, by->ptr, n, stream_);
+    }
+    case kIntReduce: {
+      const uint32_t rop = r.get<uint32_t>();
+      r.get<uint32_t>();
+      const uint64_t a = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      if (rop >= kIntReduceCount) return kBadArgument;
+      uint64_t need;
+      Buf* ba = lookup(a);
+      if (n < 0 || !mul_ok((uint64_t)n, 8, &need) || !ba || need > ba->size) return kBadHandle;
+      if (!will_read(ba)) return kLaunchFailed;
+      int64_t v = 0;
+      const int rc = dev_.int_reduce(rop, ba->ptr, n, &v, stream_);
+      waited_ = rc == 0;
+      put(out, v);
+      return rc;
+    }
+    case kIntCast: {
+      const uint32_t s = r.get<uint32_t>(), d = r.get<uint32_t>();
+      const uint64_t x = r.get<uint64_t>(), y = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      const uint64_t ssize = int_cast_size(s, d, true), dsize = int_cast_size(s, d, false);
+      if (!ssize || !dsize) return kBadArgument;
+      uint64_t nin, nout;
+      Buf *bx = lookup(x), *by = lookup(y);
+      if (n < 0 || !mul_ok((uint64_t)n, ssize, &nin) || !mul_ok((uint64_t)n, dsize, &nout) || !bx || !by ||
+          nin > bx->size || nout > by->size || by == bx)
+        return kBadHandle;
+      if (!will_read(bx) || !will_write(by, 0, nout)) return kLaunchFailed;
+      return dev_.int_cast(s, d, bx->ptr, by->ptr, n, stream_);
     }
     case kCopy: {
       const uint64_t d = r.get<uint64_t>(), doff = r.get<uint64_t>(), s = r.get<uint64_t>(), soff = r.get<uint64_t>(),

@@ -68,8 +68,46 @@ enum Op : uint32_t {
   //                 1 f64 only; p0 and p1 finite, scale and sigma >= 0, shape, a, b and df > 0 (kBadArgument
   //                 otherwise); h holds n elements (kBadHandle otherwise, as kRand)
   kRandDist,
+  // int64 arrays (csrc/kernels/integer.hip): every array element is 8 bytes, scalars travel as i64; no other op
+  // takes an int64 array, and these take no other dtype.
+  //   kRandInt      u32 kind | u32 0 | u64 h | i64 n | u64 seed | u64 off | i64 a | i64 b | f64 p
+  //                 kind 0 integers (a low, b high exclusive, b > a), 1 poisson (p lam, 0 <= lam <= 2^53),
+  //                 2 binomial (a trials, 0 <= a < 2^53; p in [0, 1]), 3 geometric (p in (0, 1]); kBadArgument
+  //                 otherwise; h holds n elements (kBadHandle otherwise, as kRand)
+  //   kIntBinary    u32 op | u32 mode | u64 a | u64 b | i64 scalar | u64 y | i64 n
+  //                 op 0 + 1 - 2 * 3 floor_divide 4 remainder 5 max 6 min; mode 0 array-array, 1 array-scalar,
+  //                 2 scalar-array (b ignored in 1 and 2); y may be a or b
+  //   kIntCompare   u32 op | u32 mode | u64 a | u64 b | i64 scalar | u64 mask_out | i64 n
+  //                 kCompare's op codes; mode 0 array-array, 1 array-scalar (b ignored); mask_out (n bytes) is
+  //                 another buffer than a and b
+  //   kIntReduce    u32 op | u32 0 | u64 a | i64 n        op 0 sum (wrapping), 1 max, 2 min; replies one i64
+  //   kIntCast      u32 src | u32 dst | u64 x | u64 y | i64 n
+  //                 (src, dst) one of (5, 1), (5, 0), (1, 5), (0, 5), (6, 5): i64 -> f64 / f32, f64 / f32 / bool
+  //                 (n bytes) -> i64; y is another buffer than x
+  kRandInt, kIntBinary, kIntCompare, kIntReduce, kIntCast,
   kOpCount
 };
+constexpr uint32_t kRandIntCount = 4;   // = BK_RINT_COUNT of csrc/kernels/beekern.h
+constexpr uint32_t kIntBinaryCount = 7, kIntReduceCount = 3;
+constexpr uint32_t kDtI64 = 5;  // not a dtype_size() code: only the int ops size int64 arrays (8 bytes an element)
+// a, b, p inside the domain of draw `kind` (the rule of bk_rand_int)
+inline bool rand_int_params_ok(uint32_t kind, int64_t a, int64_t b, double p) {
+  switch (kind) {
+    case 0: return b > a;
+    case 1: return p >= 0.0 && p <= 9007199254740992.0;  // (a NaN fails every comparison)
+    case 2: return a >= 0 && a < (1ll << 53) && p >= 0.0 && p <= 1.0;
+    case 3: return p > 0.0 && p <= 1.0;
+  }
+  return false;
+}
+// the element size of one side of a kIntCast pair; 0 for a pair bk_int_cast does not take
+inline uint64_t int_cast_size(uint32_t src, uint32_t dst, bool of_src) {
+  const bool from = src == kDtI64 && (dst == 0 || dst == 1);
+  const bool to = dst == kDtI64 && (src == 0 || src == 1 || src == 6);
+  if (!from && !to) return 0;
+  const uint32_t dt = of_src ? src : dst;
+  return dt == kDtI64 || dt == 1 ? 8 : dt == 0 ? 4 : 1;
+}
 constexpr uint32_t kDistCount = 12;  // = BK_DIST_COUNT of csrc/kernels/beekern.h
 // p0, p1 finite and inside the domain of distribution `kind` (the rule of bk_rand_dist)
 inline bool dist_params_ok(uint32_t kind, double p0, double p1) {
@@ -232,6 +270,19 @@ class Device {
   virtual int rand_dist(uint32_t, void*, int64_t, uint32_t, uint64_t, uint64_t, double, double, void*) {
     return kBadArgument;
   }
+  // int64 arrays (bk_rand_int, bk_int_binary, bk_int_compare, bk_int_reduce, bk_int_cast); the session has
+  // validated every argument.  int_reduce is synchronous like reduce: the value lands in *out
+  virtual int rand_int(uint32_t, void*, int64_t, uint64_t, uint64_t, int64_t, int64_t, double, void*) {
+    return kBadArgument;
+  }
+  virtual int int_binary(uint32_t, uint32_t, const void*, const void*, int64_t, void*, int64_t, void*) {
+    return kBadArgument;
+  }
+  virtual int int_compare(uint32_t, uint32_t, const void*, const void*, int64_t, void*, int64_t, void*) {
+    return kBadArgument;
+  }
+  virtual int int_reduce(uint32_t, const void*, int64_t, int64_t*, void*) { return kBadArgument; }
+  virtual int int_cast(uint32_t, uint32_t, const void*, void*, int64_t, void*) { return kBadArgument; }
   virtual int transpose(int sdt, int ddt, const void* in, void* out, int rows, int cols, int ldi, int ldo, void* s) = 0;
   // per-column (axis 0) / per-row (axis 1) sum or mean into y (f64 for f64 x, else f32)
   virtual int reduce_axis(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,

@@ -444,6 +444,94 @@ class HostDevice final : public Device {
     else axis_stat_t<float>(op, x, y, rows, cols, ld, axis, divisor);
     return 0;
   }
+  // the int64 ops (csrc/kernels/integer.hip): real arithmetic, comparisons,
+  // reductions and casts; a draw is a deterministic fill inside the support
+  static int64_t ibin(uint32_t op, int64_t a, int64_t b) {
+    const uint64_t ua = (uint64_t)a, ub = (uint64_t)b;
+    switch (op) {
+      case 0: return (int64_t)(ua + ub);
+      case 1: return (int64_t)(ua - ub);
+      case 2: return (int64_t)(ua * ub);
+      case 3: {
+        if (b == 0) return 0;
+        if (b == -1) return (int64_t)(0 - ua);
+        const int64_t q = a / b, r = a % b;
+        return (r != 0 && ((r < 0) != (b < 0))) ? q - 1 : q;
+      }
+      case 4: {
+        if (b == 0 || b == -1) return 0;
+        const int64_t r = a % b;
+        return (r != 0 && ((r < 0) != (b < 0))) ? r + b : r;
+      }
+      case 5: return a > b ? a : b;
+    }
+    return a < b ? a : b;
+  }
+  int int_binary(uint32_t op, uint32_t mode, const void* a, const void* b, int64_t sc, void* y, int64_t n,
+                 void*) override {
+    note("int_binary");
+    if (op >= kIntBinaryCount || mode > 2 || n < 0 || (mode == 0 && !b)) return kBadArgument;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t x = at<int64_t>(a, i), w = mode == 0 ? at<int64_t>(b, i) : sc;
+      set<int64_t>(y, i, mode == 2 ? ibin(op, w, x) : ibin(op, x, w));
+    }
+    return 0;
+  }
+  int int_compare(uint32_t op, uint32_t mode, const void* a, const void* b, int64_t sc, void* y, int64_t n,
+                  void*) override {
+    note("int_compare");
+    if (op > 5 || mode > 1 || n < 0 || (mode == 0 && !b)) return kBadArgument;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t x = at<int64_t>(a, i), w = mode == 0 ? at<int64_t>(b, i) : sc;
+      const bool t = op == 0 ? x < w : op == 1 ? x <= w : op == 2 ? x > w : op == 3 ? x >= w : op == 4 ? x == w : x != w;
+      set<uint8_t>(y, i, t ? 1 : 0);
+    }
+    return 0;
+  }
+  int int_reduce(uint32_t op, const void* a, int64_t n, int64_t* out, void*) override {
+    note("int_reduce");
+    if (op >= kIntReduceCount || n < 0) return kBadArgument;
+    int64_t r = op == 0 ? 0 : op == 1 ? INT64_MIN : INT64_MAX;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t x = at<int64_t>(a, i);
+      r = op == 0 ? (int64_t)((uint64_t)r + (uint64_t)x) : op == 1 ? (x > r ? x : r) : (x < r ? x : r);
+    }
+    *out = r;
+    return 0;
+  }
+  template <typename F>
+  static int64_t to_i64(F x) {
+    return (x >= (F)-9223372036854775808.0 && x < (F)9223372036854775808.0) ? (int64_t)x : INT64_MIN;
+  }
+  int int_cast(uint32_t s, uint32_t d, const void* x, void* y, int64_t n, void*) override {
+    note("int_cast");
+    if (!int_cast_size(s, d, true) || n < 0) return kBadArgument;
+    for (int64_t i = 0; i < n; ++i) {
+      if (s == kDtI64 && d == 1) set<double>(y, i, (double)at<int64_t>(x, i));
+      else if (s == kDtI64) set<float>(y, i, (float)at<int64_t>(x, i));
+      else if (s == 1) set<int64_t>(y, i, to_i64(at<double>(x, i)));
+      else if (s == 0) set<int64_t>(y, i, to_i64(at<float>(x, i)));
+      else set<int64_t>(y, i, at<uint8_t>(x, i) != 0 ? 1 : 0);
+    }
+    return 0;
+  }
+  // element i: integers low + (seed + off + i) mod span; poisson (seed + off + i) mod 7; binomial that mod
+  // (trials + 1); geometric 1 + that mod 5
+  int rand_int(uint32_t kind, void* y, int64_t n, uint64_t seed, uint64_t off, int64_t a, int64_t b, double p,
+               void*) override {
+    note("rand_int");
+    if (kind >= kRandIntCount || n < 0 || !rand_int_params_ok(kind, a, b, p)) return kBadArgument;
+    for (int64_t i = 0; i < n; ++i) {
+      const uint64_t w = seed + off + (uint64_t)i;
+      int64_t v;
+      if (kind == 0) v = (int64_t)((uint64_t)a + w % ((uint64_t)b - (uint64_t)a));
+      else if (kind == 1) v = p == 0.0 ? 0 : (int64_t)(w % 7);
+      else if (kind == 2) v = (int64_t)(w % ((uint64_t)a + 1));
+      else v = 1 + (int64_t)(w % 5);
+      set<int64_t>(y, i, v);
+    }
+    return 0;
+  }
   const char* last_error() override { return "host device"; }
   void info(int64_t v[5]) override {
     v[0] = 256;

@@ -182,6 +182,43 @@ BK_API int bk_reduce_axis_tail(int op, int dtype, const void* x, int64_t rows, i
                                void* out, void* ws, int tail_op, const void* tail_a, const void* tail_b, int64_t tail_n,
                                void* tail_ws, void* tail_out, hipStream_t stream);
 
+// ---- int64 arrays (integer.hip) ---------------------------------------------------------
+// Every array element is an int64_t; a pointer need only be 8-byte aligned.
+// op: 0 add, 1 subtract, 2 multiply, 3 floor_divide, 4 remainder, 5 maximum, 6 minimum; mode as bk_binary.
+// add, subtract and multiply wrap in two's complement; floor_divide and remainder follow Python's sign rule
+// (floor; the remainder takes the divisor's sign), give 0 for a zero divisor, and INT64_MIN // -1 = INT64_MIN,
+// INT64_MIN % -1 = 0 (numpy's answers on x86-64).  y may be a or b.
+BK_API int bk_int_binary(int op, int mode, const void* a, const void* b, int64_t scalar, void* y, int64_t n,
+                         hipStream_t stream);
+// op: the codes of bk_compare; mode 0 = array (op) array, 1 = array (op) scalar; mask_out: n bytes of 0 / 1
+BK_API int bk_int_compare(int op, int mode, const void* a, const void* b, int64_t scalar, void* mask_out, int64_t n,
+                          hipStream_t stream);
+// op: 0 sum (wrapping), 1 max, 2 min.  out: ONE int64 on the device.  workspace: BK_WS_REDUCE.  One launch; exact
+// and independent of the grid.  n = 0 (a still a valid pointer) is kOk and stores 0 / INT64_MIN / INT64_MAX; the
+// workspace is left ready for the next launch.
+BK_API int bk_int_reduce(int op, const void* a, int64_t n, void* workspace, void* out, hipStream_t stream);
+// exactly kI64 -> kF64, kI64 -> kF32 (round to nearest even), kF64 -> kI64, kF32 -> kI64, kBool -> kI64 (any
+// non-zero byte -> 1); another pair is kBadArgument.  Float to int truncates toward zero; NaN, +-inf and anything
+// outside [-2^63, 2^63) give INT64_MIN (numpy's astype on x86-64).
+BK_API int bk_int_cast(int src_dtype, int dst_dtype, const void* x, void* y, int64_t n, hipStream_t stream);
+// the integer-valued draws of bk_rand_int and what a, b, p mean for each (an unused one is passed as 0)
+enum BkRandInt {
+  BK_RINT_INTEGERS = 0,  // a low, b high (exclusive), b > a
+  BK_RINT_POISSON,       // p lam, 0 <= lam <= 2^53
+  BK_RINT_BINOMIAL,      // a trials, 0 <= trials < 2^53; p in [0, 1]
+  BK_RINT_GEOMETRIC,     // p in (0, 1]
+  BK_RINT_COUNT
+};
+// n int64 draws of `kind` at (seed, offset): element i depends on (seed, offset, i) and the parameters alone.
+// integers consume a counter per 4 elements (span b - a <= 2^32: Lemire's multiply-shift on one word) or per 2
+// (wider spans: on a 64-bit word); geometric one per 2; poisson (multiplication method below lam 10, Hoermann's
+// PTRS from there) and binomial (inversion below trials * min(p, 1 - p) = 10, Hoermann's BTRS from there) one per
+// element.  Every rejection loop ends after 64 Philox calls with the current candidate, clamped into the support.
+// kBadArgument before any launch for an unknown kind, a null out, n < 0 or a parameter outside its domain; n = 0
+// is kOk.
+BK_API int bk_rand_int(int kind, void* out, int64_t n, uint64_t seed, uint64_t offset, int64_t a, int64_t b, double p,
+                       hipStream_t stream);
+
 // ---- boolean masks (mask.hip): one byte per element ------------------------------------------
 // mode: 0 = array (op) array, 1 = array (op) scalar; mask_out: n bytes of 0 / 1
 BK_API int bk_compare(int op, int dtype, int mode, const void* a, const void* b, double scalar, void* mask_out,

@@ -62,5 +62,9 @@ constexpr uint32_t kTagDistF64 = 0x64697374u, kTagDistF32 = 0x64697375u;
 // that boosts a shape < 1 draw (tag + kTagBoost of its gamma substream)
 constexpr uint32_t kTagGammaX = 0x67616d30u, kTagGammaY = 0x67616d31u, kTagStudentN = 0x67616d32u;
 constexpr uint32_t kTagBoost = 0x10u;
+// bk_rand_int (integer.hip): integers by span (<= 2^32: a word per element; wider: two), the
+// poisson and binomial substreams (offset + i, tag, attempt), geometric's uniforms
+constexpr uint32_t kTagIntSmall = 0x696e7430u, kTagIntLarge = 0x696e7431u;
+constexpr uint32_t kTagPoisson = 0x706f6973u, kTagBinomial = 0x62696e6fu, kTagGeometric = 0x67656f6du;
 
 }  // namespace bk

@@ -416,6 +416,7 @@ BK_API int bk_preload(hipStream_t stream) {
     for (int x : r)
       if (rc == kOk && x != kOk) rc = x;
     if (rc == kOk) rc = bk_transpose_bf16(a, b, 64, 64, 64, 64, stream);
+    if (rc == kOk) rc = bk_int_binary(0 /*add*/, 1, c, nullptr, 1, c, 64, stream);  // integer.hip
     const int s = bk_sync(stream);
     if (rc == kOk) rc = s;
   }

@@ -278,6 +278,67 @@ def dist_rows():
         del alpha, tx, x
 
 
+def int_rows():
+    """The int64 kernels (csrc/kernels/integer.hip), n = 1e8, driver calls, medians
+    of 10: `python tools/bench_kernels.py int` (profiles/int_kernels.jsonl).  Each
+    beside a yardstick measured in the same run: the integers draws beside
+    bk_rand_uniform f64 (the same bytes written), bk_int_binary add beside
+    bk_binary f64 add, bk_int_reduce sum beside bk_reduce f64 sum (the same bytes
+    moved), poisson and binomial beside bk_rand_dist gamma(2.5) (the other
+    rejection sampler with a substream per element)."""
+    from bee_code_interpreter_fs_amd.ops import driver as D
+    from bee_code_interpreter_fs_amd.ops.array import driver
+
+    bk.init()
+    emit(kernel="device", **bk.device_info())
+    drv = driver()
+    n = 10**8
+    x, y, z = bk.empty(n, "int64"), bk.empty(n, "int64"), bk.empty(n, "int64")
+    f, g, h = bk.random.rand(n)._materialize(), bk.random.rand(n)._materialize(), bk.empty(n, "float64")
+
+    def row(kernel, fn, nbytes=n * 8, **kw):
+        ms, mn, mx = spread(fn, "bk", reps=10, warmup=2)
+        emit(kernel=kernel, n=n, ms=ms, min_ms=mn, max_ms=mx, GBps=nbytes / ms / 1e6, **kw)
+        return ms, mn, mx
+
+    def versus(name, ms, yard, y_ms, y_mn, y_mx):
+        emit(kernel=f"{name} vs {yard}", ratio=ms / y_ms, inside_yardstick_spread=bool(y_mn <= ms <= y_mx))
+
+    u = row("rand_uniform f64", lambda: drv.rand(0, h.ptr, n, h.code, 1, 0, 0.0, 1.0))
+    for name, lo, hi in (("integers(0, 6)", 0, 6), ("integers(0, 2^40)", 0, 1 << 40)):
+        ms, _, _ = row(name, lambda: drv.rand_int(D.RINT_INTEGERS, x.ptr, n, 1, 0, lo, hi, 0.0))
+        versus(name, ms, "rand_uniform f64", *u)
+    drv.rand_int(D.RINT_INTEGERS, x.ptr, n, 1, 0, -(1 << 40), 1 << 40, 0.0)
+    drv.rand_int(D.RINT_INTEGERS, y.ptr, n, 2, 0, -(1 << 40), 1 << 40, 0.0)
+    a = row("binary add f64", lambda: drv.binary(0, f.code, 0, f.ptr, g.ptr, 0.0, h.ptr, n), nbytes=n * 24)
+    ms, _, _ = row("int_binary add", lambda: drv.int_binary(0, 0, x.ptr, y.ptr, 0, z.ptr, n), nbytes=n * 24)
+    versus("int_binary add", ms, "binary add f64", *a)
+    ms, _, _ = row("int_binary floor_divide", lambda: drv.int_binary(3, 0, x.ptr, y.ptr, 0, z.ptr, n), nbytes=n * 24)
+    versus("int_binary floor_divide", ms, "binary add f64", *a)
+    ms, _, _ = row("int_compare less (array, array -> mask)", lambda: drv.int_compare(0, 0, x.ptr, y.ptr, 0, z.ptr, n),
+                   nbytes=n * 17)
+    c = row("compare less f64 (array, array -> mask)", lambda: drv.compare(0, f.code, 0, f.ptr, g.ptr, 0.0, h.ptr, n),
+            nbytes=n * 17)
+    versus("int_compare less", ms, "compare less f64", *c)
+    s = row("reduce sum f64 (incl. 8B readback)", lambda: drv.reduce(0, f.code, f.ptr, 0, n))
+    ms, _, _ = row("int_reduce sum (incl. 8B readback)", lambda: drv.int_reduce(0, x.ptr, n))
+    versus("int_reduce sum", ms, "reduce sum f64", *s)
+    ms, _, _ = row("int_cast int64 -> f64", lambda: drv.int_cast(5, 1, x.ptr, h.ptr, n), nbytes=n * 16)
+    versus("int_cast int64 -> f64", ms, "binary add f64 (24 against 16 bytes an element)", *a)
+    ga = row("rand_dist gamma(2.5) f64", lambda: drv.rand_dist(D.DIST_GAMMA, h.ptr, n, h.code, 1, 0, 2.5, 1.0))
+    for name, kind, trials, p in (("poisson(3)", D.RINT_POISSON, 0, 3.0), ("poisson(50)", D.RINT_POISSON, 0, 50.0),
+                                  ("binomial(10, 0.5)", D.RINT_BINOMIAL, 10, 0.5),
+                                  ("binomial(1000, 0.3)", D.RINT_BINOMIAL, 1000, 0.3),
+                                  ("geometric(0.2)", D.RINT_GEOMETRIC, 0, 0.2)):
+        ms, _, _ = row(name, lambda: drv.rand_int(kind, x.ptr, n, 1, 0, trials, 0, p))
+        versus(name, ms, "rand_dist gamma(2.5) f64", *ga)
+    tx = torch.empty(n, dtype=torch.int64, device="cuda")
+    for name, fn in (("torch random_(0, 6) int64", lambda: tx.random_(0, 6)),
+                     ("torch.poisson(3) f64", lambda: torch.poisson(torch.full((n,), 3.0, dtype=torch.float64, device="cuda")))):
+        ms, mn, mx = spread(fn, "torch", reps=10, warmup=2)
+        emit(kernel=name, n=n, ms=ms, min_ms=mn, max_ms=mx, GBps=n * 8 / ms / 1e6)
+
+
 def emit(**kw):
     print(json.dumps(kw), flush=True)
 
@@ -363,5 +424,5 @@ def main():
 
 
 if __name__ == "__main__":
-    modes = {"masks": mask_rows, "stats": stats_rows, "axis": axis_rows, "dist": dist_rows}
+    modes = {"masks": mask_rows, "stats": stats_rows, "axis": axis_rows, "dist": dist_rows, "int": int_rows}
     modes[sys.argv[1]]() if len(sys.argv) == 2 and sys.argv[1] in modes else main()
