@@ -64,11 +64,11 @@ def _targets() -> List[Target]:
         Target(
             name="beekern",
             output=os.path.join(PKG, "ops", "lib", "libbeekern.so"),
-            sources=[os.path.join(k, f) for f in ("random.hip", "elementwise.hip", "reduce.hip", "mask.hip", "integer.hip", "stats.hip", "axis.hip", "gemm_bf16.hip", "gemm_bf16_256.hip", "gemm_bf16_256x.hip", "gemm_fp.hip", "runtime.cpp")],
+            sources=[os.path.join(k, f) for f in ("random.hip", "elementwise.hip", "reduce.hip", "mask.hip", "integer.hip", "stats.hip", "sort.hip", "axis.hip", "gemm_bf16.hip", "gemm_bf16_256.hip", "gemm_bf16_256x.hip", "gemm_fp.hip", "runtime.cpp")],
             compiler=HIPCC,
             compile_flags=HIP_FLAGS,
             link_flags=[f"--offload-arch={ARCH}", "-shared", "-fPIC"],
-            headers=[os.path.join(k, f) for f in ("beekern.h", "bk_common.hpp", "bk_dispatch.hpp", "bk_philox.hpp", "bk_ticket.hpp", "bk_reduce_ops.hpp", "bk_binary_op.hpp", "gemm256_impl.hpp", "gemm256w4_impl.hpp")],
+            headers=[os.path.join(k, f) for f in ("beekern.h", "bk_common.hpp", "bk_dispatch.hpp", "bk_philox.hpp", "bk_ticket.hpp", "bk_keys.hpp", "bk_reduce_ops.hpp", "bk_binary_op.hpp", "gemm256_impl.hpp", "gemm256w4_impl.hpp")],
             hip=True,
         ),
     ]

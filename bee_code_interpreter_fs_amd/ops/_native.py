@@ -115,6 +115,10 @@ SIGNATURES = {
     "bk_select": ([c_int, c_vp, c_i64, ctypes.POINTER(c_i64), c_int, c_vp, c_vp, c_vp], c_int),
     "bk_histogram_max_bins": ([], c_int),
     "bk_histogram": ([c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp], c_int),
+    "bk_sort_workspace_bytes": ([c_int, c_i64, c_int], c_i64),
+    "bk_sort": ([c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp], c_int),
+    "bk_arg_reduce": ([c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp], c_int),
+    "bk_take": ([c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp], c_int),
     "bk_reduce_axis": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp], c_int),
     "bk_reduce_axis_cast": ([c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_int, c_vp, c_vp, c_vp], c_int),
     "bk_reduce_axis_tail": (

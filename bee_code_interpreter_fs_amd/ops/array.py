@@ -19,6 +19,11 @@ array without sorting or copying it (``csrc/kernels/stats.hip``: a radix
 select of a few ranks, a histogram counted in LDS); they read a ``.T`` view in
 place and return host scalars / ndarrays typed as numpy's.
 
+``sort`` / ``argsort`` (1-D, always stable), ``argmax`` / ``argmin`` (the flat
+index) and ``take`` / ``x[idx]`` (1-D, by an int64 index array) order and
+reorder arrays on the device (``csrc/kernels/sort.hip``), in numpy's order:
+NaNs last, ``-0.0 == +0.0``, ties in index order.
+
 2-D arrays: the binary operations broadcast an ``(R, C)`` array against a
 ``(C,)``, ``(1, C)`` or ``(R, 1)`` one of the same dtype in one pass, and
 ``amax`` / ``amin`` / ``var`` / ``std`` (like ``sum`` / ``mean``) reduce along
@@ -325,7 +330,12 @@ class DeviceArray:
 
     def __getitem__(self, key) -> "DeviceArray":
         """``x[mask]``: the elements where the bool array ``mask`` (of x's
-        shape) is true, 1-D in C order.  No other indexing on the device."""
+        shape) is true, 1-D in C order.  ``x[idx]`` of a 1-D array: ``take(x, idx)`` for an int64
+        DeviceArray or a host integer list / ndarray.  No other indexing on the device."""
+        if isinstance(key, DeviceArray) and key.dtype == "int64" and self.ndim == 1:
+            return take(self, key)
+        if self.ndim == 1 and _is_host_index(key):
+            return take(self, key)
         if not isinstance(key, DeviceArray) or key.dtype != "bool":
             raise TypeError("beekern arrays are indexed by a bool DeviceArray of the same shape only")
         if key.shape != self.shape:
@@ -336,6 +346,15 @@ class DeviceArray:
             # (int64 elements move by size, as float64's)
             driver().compress(_bits_code(self), self.ptr, key.ptr, self.size, out.ptr, count)
         return out
+
+    def argsort(self, kind=None) -> "DeviceArray":
+        return argsort(self, kind)
+
+    def argmax(self, axis=None):
+        return argmax(self, axis)
+
+    def argmin(self, axis=None):
+        return argmin(self, axis)
 
     def sum(self, axis: Optional[int] = None, keepdims: bool = False):
         return sum(self, axis, keepdims)
@@ -1310,6 +1329,121 @@ def _int_where(mask: DeviceArray, a, b) -> DeviceArray:
         arrays.append(v)
     out = DeviceArray(mask.shape, "int64")
     driver().where(DTYPE_CODES["float64"], mask.ptr, 0, arrays[0].ptr, arrays[1].ptr, 0.0, 0.0, out.ptr, mask.size)
+    return out
+
+
+# ---- sorting, arg-reductions, gather (csrc/kernels/sort.hip) -------------------------
+# numpy's order: floats numerically with -0.0 == +0.0 a tie and NaNs last, int64 signed, ties in index order (the
+# sort is always stable).  np.sort / np.argsort / np.argmax / np.argmin / np.take of a device array are not routed
+# here yet: they stay host fallbacks that warn (ops/npinterop.py).
+MAX_SORT_N = 0x7FFFFFFF  # = BK_MAX_SORT_N (csrc/kernels/beekern.h), driver.MAX_SORT_N
+_SORTABLE = ("float32", "float64", "bfloat16", "int64")
+
+
+def _sort_operand(what: str, x, one_d: bool) -> DeviceArray:
+    x = _as_operand(x)
+    if x.dtype not in _SORTABLE:
+        raise TypeError(f"beekern {what}: float32 / float64 / bfloat16 / int64 arrays only, got {x.dtype}")
+    if one_d and x.ndim != 1:
+        raise TypeError(f"beekern {what}: 1-D arrays only, got ndim {x.ndim} (no axis sorts yet)")
+    if x._transposed:
+        raise TypeError(f"beekern {what}: not on a .T view (copy it first: its C-order elements are not in the buffer's order)")
+    x._materialize()
+    return x
+
+
+def _sort(what: str, x, want_sorted: bool, want_index: bool):
+    from .driver import sort_workspace_bytes
+
+    x = _sort_operand(what, x, True)
+    n = x.size
+    if n > MAX_SORT_N:
+        raise TypeError(f"beekern {what}: at most {MAX_SORT_N} elements a call (BK_MAX_SORT_N), got {n}")
+    out = DeviceArray((n,), x.dtype) if want_sorted else None
+    index = DeviceArray((n,), "int64") if want_index else None
+    if n:
+        ws = _Buffer(sort_workspace_bytes(x.code, n, want_index))
+        driver().sort(x.code, x.ptr, n, out.ptr if out is not None else 0, index.ptr if index is not None else 0, ws.ptr)
+    return out, index
+
+
+def sort(x, kind=None) -> DeviceArray:  # noqa: A001 - numpy-compatible name
+    """np.sort(x) of a 1-D array, in x's dtype (``kind`` is accepted and ignored: the sort is stable)."""
+    return _sort("sort", x, True, False)[0]
+
+
+def argsort(x, kind=None) -> DeviceArray:
+    """np.argsort(x, kind="stable") of a 1-D array as an int64 array."""
+    return _sort("argsort", x, False, True)[1]
+
+
+def _arg_reduce(what: str, x, axis):
+    if axis is not None:
+        raise TypeError(f"beekern {what}: axis= is not there yet (the flat index of the whole array only)")
+    x = _sort_operand(what, x, False)
+    if x.size == 0:
+        raise ValueError(f"attempt to get {what} of an empty sequence")
+    v = driver().arg_reduce(0 if what == "argmax" else 1, x.code, x.ptr, x.size)
+    m = numpy_loaded()
+    return m.int64(v) if m is not None else v
+
+
+def argmax(x, axis=None):
+    """np.argmax(x): the flat C-order index of the first maximum (the first NaN if there is one) as ``np.int64``."""
+    return _arg_reduce("argmax", x, axis)
+
+
+def argmin(x, axis=None):
+    """np.argmin(x): the flat C-order index of the first minimum (the first NaN if there is one) as ``np.int64``."""
+    return _arg_reduce("argmin", x, axis)
+
+
+def _is_host_index(key) -> bool:
+    """A non-empty list or ndarray of integers (not bools): what ``x[key]`` gathers by."""
+    m = numpy_loaded()
+    if isinstance(key, list):
+        return len(key) > 0 and not [k for k in key if isinstance(k, bool) or not is_integer(k)]
+    return m is not None and isinstance(key, m.ndarray) and key.dtype.kind in "iu"
+
+
+def _index_operand(x: DeviceArray, idx) -> DeviceArray:
+    """``idx`` as an int64 device array: one as it is; a host integer list / ndarray checked against x's length
+    (numpy's IndexError, before anything is uploaded) and uploaded."""
+    if isinstance(idx, DeviceArray):
+        if idx.dtype != "int64":
+            raise TypeError(f"beekern take: the index is an int64 array, got {idx.dtype}")
+        if idx._transposed:
+            raise TypeError("beekern take: not by a .T view")
+        idx._materialize()
+        return idx
+    host = np.asarray(idx)
+    if host.size == 0:
+        host = host.astype(np.int64)  # (an empty list is float64 to numpy)
+    if host.dtype.kind not in "iu":
+        raise TypeError(f"beekern take: integer indices only, got {host.dtype}")
+    if host.dtype.kind == "u" and host.size and int(host.max()) > _I64_MAX:
+        raise IndexError(f"index {int(host.max())} is out of bounds for axis 0 with size {x.size}")
+    host = host.astype(np.int64)
+    bad = (host < -x.size) | (host >= x.size)
+    if bad.any():
+        raise IndexError(f"index {int(host[bad].flat[0])} is out of bounds for axis 0 with size {x.size}")
+    return asarray(host, dtype="int64")
+
+
+def take(x, idx) -> DeviceArray:
+    """np.take(x, idx) of a 1-D array: ``x[idx]`` for an int64 index array (a DeviceArray, or a host integer list /
+    ndarray), negative indices from the end, in idx's shape.  IndexError if an index is outside [-len(x), len(x))."""
+    x = _as_operand(x)
+    if x.ndim != 1:
+        raise TypeError(f"beekern take: 1-D arrays only, got ndim {x.ndim}")
+    if x.dtype not in _SUPPORTED:
+        raise TypeError(f"beekern take: no kernel for {x.dtype} arrays")
+    x._materialize()
+    idx = _index_operand(x, idx)
+    out = DeviceArray(idx.shape, x.dtype)
+    bad = driver().take(_bits_code(x), x.ptr, x.size, idx.ptr, idx.size, out.ptr)
+    if bad:
+        raise IndexError(f"index out of bounds for axis 0 with size {x.size} ({bad} of the {idx.size} indices)")
     return out
 
 

@@ -39,6 +39,21 @@ _STATS_EDGES_AT = 512
 _STATS_COUNTS_AT = _STATS_EDGES_AT + (MAX_BINS + 1) * 8
 _STATS_SCRATCH_BYTES = _STATS_COUNTS_AT + MAX_BINS * 8
 
+# bk_sort: at most MAX_SORT_N elements a call (BK_MAX_SORT_N), and the bytes of its scratch
+# (bk_sort_workspace_bytes of csrc/kernels/sort.hip; the broker checks its own copy against the library's)
+MAX_SORT_N = 0x7FFFFFFF
+_SORT_WS_HEADER = 256 + 256 * 4 + 512 * 256 * 4
+_SORT_DTYPES = {0: 4, 1: 8, 2: 2, 5: 8}
+
+
+def sort_workspace_bytes(dt: int, n: int, with_index: bool) -> int:
+    """The size of ``sort``'s scratch buffer; 0 for a dtype or n it does not take."""
+    if dt not in _SORT_DTYPES or not 0 <= n <= MAX_SORT_N:
+        return 0
+    r16 = lambda b: (b + 15) & ~15  # noqa: E731
+    return _SORT_WS_HEADER + 2 * r16(n * _SORT_DTYPES[dt]) + (2 * r16(n * 4) if with_index else 0)
+
+
 # the kernels' scratch workspaces: enum BkWorkspace of csrc/kernels/beekern.h
 WS_REDUCE, WS_REDUCE_AXIS, WS_AXIS_STAT, WS_COMPRESS, WS_SELECT, WS_HISTOGRAM, WS_COUNT = range(7)
 
@@ -224,6 +239,31 @@ class NativeDriver:
         """int64 -> f64 / f32, f64 / f32 / bool -> int64 (dtype codes)."""
         check(self.lib.bk_int_cast(s, d, _vp(x), _vp(y), n, self.stream), "bk_int_cast")
 
+    # ---- sorting, arg-reductions, gather (csrc/kernels/sort.hip) ------------------------
+    def sort(self, dt: int, x: int, n: int, sorted_out: int, index_out: int, ws: int) -> None:
+        """sorted_out = np.sort(x) and / or index_out (int64) = np.argsort(x, kind="stable"); 0: not wanted.
+        ws: ``sort_workspace_bytes(dt, n, bool(index_out))`` bytes of scratch."""
+        check(self.lib.bk_sort(dt, _vp(x), n, _vp(sorted_out) if sorted_out else None,
+                               _vp(index_out) if index_out else None, _vp(ws),
+                               sort_workspace_bytes(dt, n, bool(index_out)), self.stream), "bk_sort")
+
+    def arg_reduce(self, op: int, dt: int, x: int, n: int) -> int:
+        """op 0 np.argmax, 1 np.argmin of the n elements (n >= 1), as a Python int."""
+        check(self.lib.bk_arg_reduce(op, dt, _vp(x), n, _vp(self.workspaces[WS_REDUCE]), _vp(self.scalar), self.stream),
+              "bk_arg_reduce")
+        out = np.zeros(1, np.int64)
+        self.d2h(self.scalar, out)
+        return int(out[0])
+
+    def take(self, dt: int, x: int, n: int, idx: int, m: int, out: int) -> int:
+        """out[i] = x[idx[i]] for m int64 indices in [-n, n); returns the number of indices outside it
+        (their elements are zero, nothing is read through them)."""
+        check(self.lib.bk_take(dt, _vp(x), n, _vp(idx), m, _vp(out), _vp(self.workspaces[WS_REDUCE]), _vp(self.scalar),
+                               self.stream), "bk_take")
+        bad = np.zeros(1, np.int64)
+        self.d2h(self.scalar, bad)
+        return int(bad[0])
+
     # ---- order statistics and histograms (csrc/kernels/stats.hip) ---------------------
     def _stats_scratch(self) -> int:
         """Device scratch of the two ops: 33 f64 select results, then the
@@ -320,7 +360,7 @@ def _info_dict(v, arch: str) -> dict:
 (HELLO, ALLOC, FREE, WRITE, READ, RAND, UNARY, BINARY, CAST, FILL, REDUCE, GEMM, TRANSPOSE, SYNC, MEMSTATS, INFO,
  COPY, RAND_REDUCE, ALLOC_AT, REDUCE_AXIS, GEMM_FP, COMPARE, COMPARE_COUNT, MASK_LOGICAL, WHERE,
  COMPRESS, SELECT, HISTOGRAM, BROADCAST, AXIS_STAT, RAND_DIST, RAND_INT, INT_BINARY, INT_COMPARE, INT_REDUCE,
- INT_CAST) = range(1, 37)
+ INT_CAST, SORT, ARG_REDUCE, TAKE) = range(1, 40)
 _HDR = struct.Struct("<IIQ")
 _NO_REPLY = 1  # request flag: no response unless a later request collects an error
 _RHDR = struct.Struct("<iIQ")
@@ -605,6 +645,17 @@ class BrokerDriver:
 
     def int_cast(self, s, d, x, y, n) -> None:
         self._post(INT_CAST, struct.pack("<IIQQq", s, d, x, y, n))
+
+    # sorting, arg-reductions, gather: payload layouts beside the op enum in csrc/executor/broker_core.hpp
+    def sort(self, dt, x, n, sorted_out, index_out, ws) -> None:
+        flags = (1 if sorted_out else 0) | (2 if index_out else 0)
+        self._post(SORT, struct.pack("<IIQqQQQ", dt, flags, x, n, sorted_out or 0, index_out or 0, ws))
+
+    def arg_reduce(self, op, dt, x, n) -> int:
+        return struct.unpack("<q", self._call(ARG_REDUCE, struct.pack("<IIQq", op, dt, x, n)))[0]
+
+    def take(self, dt, x, n, idx, m, out) -> int:
+        return struct.unpack("<q", self._call(TAKE, struct.pack("<IIQqQqQ", dt, 0, x, n, idx, m, out)))[0]
 
     # order statistics and histograms: both reply, like REDUCE
     def select(self, dt, x, n, ranks) -> tuple:

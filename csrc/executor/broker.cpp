@@ -21,7 +21,7 @@ namespace bee {
 
 // (broker_core.hpp stays HIP-free and keeps its own copies of the limits)
 static_assert(broker::kMaxBins == BK_MAX_BINS && broker::kMaxRanks == BK_MAX_RANKS &&
-                  broker::kTailMaxVectors == BK_TAIL_MAX_VECTORS,
+                  broker::kTailMaxVectors == BK_TAIL_MAX_VECTORS && broker::kMaxSortN == BK_MAX_SORT_N,
               "broker_core.hpp and csrc/kernels/beekern.h disagree on a limit");
 
 namespace {
@@ -57,6 +57,7 @@ class HipDevice final : public broker::Device {
   X(broadcast) X(axis_stat)                                        /* matrix against vector, axis statistics (axis.hip) */ \
   X(rand_dist)                                                     /* continuous distributions (random.hip) */ \
   X(rand_int) X(int_binary) X(int_compare) X(int_reduce) X(int_cast) /* int64 arrays (integer.hip) */                \
+  X(sort_workspace_bytes) X(sort) X(arg_reduce) X(take)            /* sorting, arg-reductions, gather (sort.hip) */  \
   X(reduce_axis_cast) X(reduce_axis_tail) X(gemm_bf16_tn_tail)     /* a producer with its cast or closing reduce */
   struct Bk {
 #define X(name) decltype(&bk_##name) name = nullptr;
@@ -282,6 +283,15 @@ class HipDevice final : public broker::Device {
     BEE_BK_ENTRY_POINTS(X)
 #undef X
 #undef BEE_BK_ENTRY_POINTS
+    // the sessions size bk_sort's scratch with broker_core.hpp's HIP-free copy of the library's formula
+    for (uint32_t dt = 0; dt < 8; ++dt)
+      for (int64_t n : {(int64_t)-1, (int64_t)0, (int64_t)1, (int64_t)4097, (int64_t)100000003, broker::kMaxSortN,
+                        broker::kMaxSortN + 1})
+        for (int wi = 0; wi < 2; ++wi)
+          if ((uint64_t)bk.sort_workspace_bytes((int)dt, n, wi) != broker::sort_workspace_bytes(dt, n, wi != 0)) {
+            *err = "broker_core.hpp and libbeekern.so disagree on bk_sort's workspace size";
+            return false;
+          }
     return true;
   }
 
@@ -618,6 +628,36 @@ class HipDevice final : public broker::Device {
   }
   int int_cast(uint32_t sdt, uint32_t ddt, const void* x, void* y, int64_t n, void* s) override {
     return timed(s, st(s), [&](hipStream_t q) { return bk.int_cast((int)sdt, (int)ddt, x, y, n, q); });
+  }
+  // sorting, arg-reductions, gather (sort.hip)
+  int sort(uint32_t dt, const void* x, int64_t n, void* sorted, void* index, void* ws, uint64_t ws_bytes,
+           void* s) override {
+    return timed(s, st(s),
+                 [&](hipStream_t q) { return bk.sort((int)dt, x, n, sorted, index, ws, (int64_t)ws_bytes, q); });
+  }
+  // the result slot's 8 bytes as an int64 (fetch() reads them as a double)
+  int fetch_i64(Ctx* c, int rc, int64_t* out) {
+    if (rc != 0) return rc;
+    if (c->slot == nullptr) {
+      if (hipMemcpyAsync(out, c->scalar, 8, hipMemcpyDeviceToHost, c->s) != hipSuccess || !wait(c))
+        return broker::kLaunchFailed;
+      return 0;
+    }
+    if (!wait(c)) return broker::kLaunchFailed;
+    *out = *(volatile int64_t*)c->slot;
+    return 0;
+  }
+  int arg_reduce(uint32_t op, uint32_t dt, const void* x, int64_t n, int64_t* out, void* s) override {
+    Ctx* c = (Ctx*)s;
+    return fetch_i64(c, timed(s, st(s), [&](hipStream_t q) {
+      return bk.arg_reduce((int)op, (int)dt, x, n, c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
+    }), out);
+  }
+  int take(uint32_t dt, const void* x, int64_t n, const void* idx, int64_t m, void* y, int64_t* out, void* s) override {
+    Ctx* c = (Ctx*)s;
+    return fetch_i64(c, timed(s, st(s), [&](hipStream_t q) {
+      return bk.take((int)dt, x, n, idx, m, y, c->ws[BK_WS_REDUCE], c->slot ? (void*)c->slot : c->scalar, q);
+    }), out);
   }
   int mask_logical(uint32_t op, const void* a, const void* b, void* y, int64_t n, void* s) override {
     return timed(s, st(s),

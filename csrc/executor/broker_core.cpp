@@ -19,7 +19,7 @@ const char* op_name(uint32_t op) {
                                       "bk.reduce_axis", "bk.gemm_fp", "bk.compare", "bk.compare_count",
                                       "bk.mask_logical", "bk.where", "bk.compress", "bk.select", "bk.histogram",
                                       "bk.broadcast", "bk.axis_stat", "bk.rand_dist", "bk.rand_int", "bk.int_binary",
-                                      "bk.int_compare", "bk.int_reduce", "bk.int_cast"};
+                                      "bk.int_compare", "bk.int_reduce", "bk.int_cast", "bk.sort", "bk.arg_reduce", "bk.take"};
   return op < sizeof(names) / sizeof(names[0]) ? names[op] : names[0];
 }
 
@@ -257,6 +257,27 @@ Weight frame_weight(uint32_t op, const char* payload, uint64_t len) {
       const int64_t n = r.get<int64_t>();
       const auto size = [](uint32_t dt) -> int64_t { return dt == 0 ? 4 : dt == kDtBool ? 1 : 8; };
       return weigh(short_bytes(n, size(s) + size(d)));
+    }
+    case kSort: {  // two launches per byte of the key, each reading the keys once; the scatter writes them too
+      const uint32_t dt = r.get<uint32_t>();
+      r.get<uint32_t>(), r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      const int64_t es = (int64_t)sort_elem_size(dt);
+      return weigh(short_bytes(n, es ? es + 4 : 12, 3 * (es ? es : 8)));
+    }
+    case kArgReduce: {  // as kReduce
+      r.get<uint32_t>();
+      const uint32_t dt = r.get<uint32_t>();
+      r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      return weigh(short_bytes(n, dt == kDtI64 ? 8 : elem(dt)));
+    }
+    case kTake: {  // m indices read, m elements gathered and written
+      const uint32_t dt = r.get<uint32_t>();
+      r.get<uint32_t>(), r.get<uint64_t>(), r.get<int64_t>(), r.get<uint64_t>();
+      const int64_t m = r.get<int64_t>();
+      const int64_t es = (int64_t)sort_elem_size(dt, true);
+      return weigh(short_bytes(m, 8 + 2 * (es ? es : 8)));
     }
   }
   return kLong;  // an unknown op launches nothing; counted as long, it moves nothing to the priority lane
@@ -1047,6 +1068,68 @@ int32_t Session::dispatch(uint32_t op, const char* payload, uint64_t len, std::v
         return kBadHandle;
       if (!will_read(bx) || !will_write(by, 0, nout)) return kLaunchFailed;
       return dev_.int_cast(s, d, bx->ptr, by->ptr, n, stream_);
+    }
+    case kSort: {
+      const uint32_t dt = r.get<uint32_t>(), sflags = r.get<uint32_t>();
+      const uint64_t x = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      const uint64_t sh = r.get<uint64_t>(), ih = r.get<uint64_t>(), wh = r.get<uint64_t>();
+      if (!r.ok) return kProtocol;
+      const uint64_t es = sort_elem_size(dt);
+      if (!es || sflags == 0 || sflags > 3 || n < 0 || n > kMaxSortN) return kBadArgument;
+      const bool want_sorted = sflags & 1, want_index = sflags & 2;
+      const uint64_t need = (uint64_t)n * es, ineed = (uint64_t)n * 8;  // (n < 2^31: no wrap)
+      const uint64_t wneed = sort_workspace_bytes(dt, n, want_index);
+      Buf *bx = lookup(x), *bs = want_sorted ? lookup(sh) : nullptr, *bi = want_index ? lookup(ih) : nullptr,
+          *bw = lookup(wh);
+      if (!bx || !bw || need > bx->size || wneed > bw->size || (want_sorted && (!bs || need > bs->size)) ||
+          (want_index && (!bi || ineed > bi->size)) || bw == bx || bs == bx || bi == bx || (bs && (bs == bi || bs == bw)) ||
+          (bi && bi == bw))
+        return kBadHandle;
+      // the scratch is read back by the passes only where they wrote it; scrubbed first all the same, like a read
+      if (!will_read(bx) || !will_read(bw) || (bs && !will_write(bs, 0, need)) || (bi && !will_write(bi, 0, ineed)))
+        return kLaunchFailed;
+      if (n == 0) return kOk;
+      return dev_.sort(dt, bx->ptr, n, bs ? bs->ptr : nullptr, bi ? bi->ptr : nullptr, bw->ptr, bw->size, stream_);
+    }
+    case kArgReduce: {
+      const uint32_t aop = r.get<uint32_t>(), dt = r.get<uint32_t>();
+      const uint64_t x = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      if (!r.ok) return kProtocol;
+      const uint64_t es = sort_elem_size(dt);
+      if (aop > 1 || !es || n < 1) return kBadArgument;
+      uint64_t need;
+      Buf* bx = lookup(x);
+      if (!mul_ok((uint64_t)n, es, &need) || !bx || need > bx->size) return kBadHandle;
+      if (!will_read(bx)) return kLaunchFailed;
+      int64_t v = 0;
+      const int rc = dev_.arg_reduce(aop, dt, bx->ptr, n, &v, stream_);
+      waited_ = rc == 0;
+      put(out, v);
+      return rc;
+    }
+    case kTake: {
+      const uint32_t dt = r.get<uint32_t>(), zero = r.get<uint32_t>();
+      const uint64_t x = r.get<uint64_t>();
+      const int64_t n = r.get<int64_t>();
+      const uint64_t ih = r.get<uint64_t>();
+      const int64_t m = r.get<int64_t>();
+      const uint64_t y = r.get<uint64_t>();
+      if (!r.ok) return kProtocol;
+      const uint64_t es = sort_elem_size(dt, true);
+      if (!es || zero != 0 || n < 0 || m < 0) return kBadArgument;
+      uint64_t need, ineed, oneed;
+      Buf *bx = lookup(x), *bi = lookup(ih), *by = lookup(y);
+      if (!mul_ok((uint64_t)n, es, &need) || !mul_ok((uint64_t)m, 8, &ineed) || !mul_ok((uint64_t)m, es, &oneed) || !bx ||
+          !bi || !by || need > bx->size || ineed > bi->size || oneed > by->size || by == bx || by == bi)
+        return kBadHandle;
+      if (!will_read(bx) || !will_read(bi) || !will_write(by, 0, oneed)) return kLaunchFailed;
+      int64_t bad = 0;
+      const int rc = dev_.take(dt, bx->ptr, n, bi->ptr, m, by->ptr, &bad, stream_);
+      waited_ = rc == 0;
+      put(out, bad);
+      return rc;
     }
     case kCopy: {
       const uint64_t d = r.get<uint64_t>(), doff = r.get<uint64_t>(), s = r.get<uint64_t>(), soff = r.get<uint64_t>(),

@@ -85,11 +85,37 @@ enum Op : uint32_t {
   //                 (src, dst) one of (5, 1), (5, 0), (1, 5), (0, 5), (6, 5): i64 -> f64 / f32, f64 / f32 / bool
   //                 (n bytes) -> i64; y is another buffer than x
   kRandInt, kIntBinary, kIntCompare, kIntReduce, kIntCast,
+  // sorting, arg-reductions and gather (csrc/kernels/sort.hip); dt 0 f32, 1 f64, 2 bf16 or 5 i64 (kTake also 6,
+  // bool: elements move by size).  numpy's order: NaNs last, -0.0 == +0.0, int64 signed, ties in index order.
+  //   kSort         u32 dt | u32 flags | u64 x | i64 n | u64 sorted | u64 index | u64 ws
+  //                 flags bit 0: sorted (n elements of dt) is present, bit 1: index (n i64) is present, at least
+  //                 one of them (an absent one's handle is ignored); 0 <= n <= kMaxSortN; ws holds at least
+  //                 sort_workspace_bytes(dt, n, bit 1); the outputs and ws are other buffers than x and than each
+  //                 other; no reply
+  //   kArgReduce    u32 op | u32 dt | u64 x | i64 n      op 0 argmax, 1 argmin; n >= 1; replies one i64
+  //   kTake         u32 dt | u32 0 | u64 x | i64 n | u64 idx | i64 m | u64 out
+  //                 out[i] = x[idx[i]] for m i64 indices in [-n, n); out (m elements) is another buffer than x and
+  //                 idx; replies one i64, the number of indices outside the range (their elements are zero)
+  kSort, kArgReduce, kTake,
   kOpCount
 };
 constexpr uint32_t kRandIntCount = 4;   // = BK_RINT_COUNT of csrc/kernels/beekern.h
 constexpr uint32_t kIntBinaryCount = 7, kIntReduceCount = 3;
 constexpr uint32_t kDtI64 = 5;  // not a dtype_size() code: only the int ops size int64 arrays (8 bytes an element)
+constexpr int64_t kMaxSortN = 0x7fffffff;  // = BK_MAX_SORT_N of csrc/kernels/beekern.h
+// the element size of a dtype the sort family takes (take_too: kTake's bool as well); 0 for any other code
+inline uint64_t sort_elem_size(uint32_t dt, bool take_too = false) {
+  return dt == 0 ? 4 : dt == 1 || dt == kDtI64 ? 8 : dt == 2 ? 2 : (take_too && dt == 6) ? 1 : 0;
+}
+// bk_sort's scratch: a header (ticket, digit bases, a 512-block table of 256 counts), two key buffers and, with an
+// index, two buffers of 32-bit indices, each rounded up to 16 bytes (csrc/kernels/sort.hip
+// bk_sort_workspace_bytes, ops/driver.py sort_workspace_bytes); 0 for a dtype or n bk_sort does not take
+inline uint64_t sort_workspace_bytes(uint32_t dt, int64_t n, bool with_index) {
+  const uint64_t es = sort_elem_size(dt);
+  if (!es || n < 0 || n > kMaxSortN) return 0;
+  const auto r16 = [](uint64_t b) { return (b + 15) & ~15ull; };
+  return 256 + 256 * 4 + 512 * 256 * 4 + 2 * r16((uint64_t)n * es) + (with_index ? 2 * r16((uint64_t)n * 4) : 0);
+}
 // a, b, p inside the domain of draw `kind` (the rule of bk_rand_int)
 inline bool rand_int_params_ok(uint32_t kind, int64_t a, int64_t b, double p) {
   switch (kind) {
@@ -283,6 +309,12 @@ class Device {
   }
   virtual int int_reduce(uint32_t, const void*, int64_t, int64_t*, void*) { return kBadArgument; }
   virtual int int_cast(uint32_t, uint32_t, const void*, void*, int64_t, void*) { return kBadArgument; }
+  // sorting, arg-reductions and gather (bk_sort, bk_arg_reduce, bk_take); the session has validated every
+  // argument.  sort(dt, x, n, sorted or null, index or null, ws, ws_bytes) is asynchronous; arg_reduce and take are
+  // synchronous like reduce: the index / the count of bad indices lands in *out
+  virtual int sort(uint32_t, const void*, int64_t, void*, void*, void*, uint64_t, void*) { return kBadArgument; }
+  virtual int arg_reduce(uint32_t, uint32_t, const void*, int64_t, int64_t*, void*) { return kBadArgument; }
+  virtual int take(uint32_t, const void*, int64_t, const void*, int64_t, void*, int64_t*, void*) { return kBadArgument; }
   virtual int transpose(int sdt, int ddt, const void* in, void* out, int rows, int cols, int ldi, int ldo, void* s) = 0;
   // per-column (axis 0) / per-row (axis 1) sum or mean into y (f64 for f64 x, else f32)
   virtual int reduce_axis(uint32_t op, uint32_t dt, const void* x, void* y, int64_t rows, int64_t cols, int64_t ld,

@@ -532,6 +532,68 @@ class HostDevice final : public Device {
     }
     return 0;
   }
+  // sorting, arg-reductions, gather (csrc/kernels/sort.hip): real answers under numpy's order -- the key of an
+  // element orders it (floats: -0.0 folded onto +0.0, negatives flipped, NaNs all the largest key; int64: the
+  // sign bit flipped), a stable sort of the keys
+  static uint64_t sort_key(uint32_t dt, const void* x, int64_t i) {
+    if (dt == kDtI64) return at<uint64_t>(x, i) ^ (1ull << 63);
+    const int bits = dt == 1 ? 64 : dt == 0 ? 32 : 16;
+    uint64_t u = dt == 1 ? at<uint64_t>(x, i) : dt == 0 ? (uint64_t)at<uint32_t>(x, i) : (uint64_t)at<uint16_t>(x, i);
+    const uint64_t sign = 1ull << (bits - 1), all = bits == 64 ? ~0ull : (1ull << bits) - 1;
+    const uint64_t inf = dt == 1 ? 0x7ff0000000000000ull : dt == 0 ? 0x7f800000ull : 0x7f80ull;
+    if ((u & ~sign & all) == 0) u = 0;
+    if ((u & ~sign & all) > inf) return all;
+    return (u & sign) ? (~u & all) : (u | sign);
+  }
+  int sort(uint32_t dt, const void* x, int64_t n, void* sorted, void* index, void* ws, uint64_t ws_bytes,
+           void*) override {
+    note("sort");
+    const uint64_t es = sort_elem_size(dt);
+    if (!es || n < 0 || n > kMaxSortN || (!sorted && !index) || !x || !ws ||
+        ws_bytes < sort_workspace_bytes(dt, n, index != nullptr))
+      return kBadArgument;
+    std::vector<uint64_t> key((size_t)n);
+    std::vector<int64_t> order((size_t)n);
+    for (int64_t i = 0; i < n; ++i) key[(size_t)i] = sort_key(dt, x, i), order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return key[(size_t)a] < key[(size_t)b]; });
+    memset(ws, 0x5c, (size_t)sort_workspace_bytes(dt, n, index != nullptr));  // the scratch is the call's to scribble on
+    for (int64_t i = 0; i < n; ++i) {
+      if (sorted) memcpy((char*)sorted + (uint64_t)i * es, (const char*)x + (uint64_t)order[(size_t)i] * es, es);
+      if (index) set<int64_t>(index, i, order[(size_t)i]);
+    }
+    return 0;
+  }
+  int arg_reduce(uint32_t op, uint32_t dt, const void* x, int64_t n, int64_t* out, void*) override {
+    note("arg_reduce");
+    if (op > 1 || !sort_elem_size(dt) || n < 1) return kBadArgument;
+    const uint64_t top = dt == kDtI64 || dt == 1 ? ~0ull : dt == 0 ? 0xffffffffull : 0xffffull;
+    int64_t best = 0;
+    uint64_t bk = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      uint64_t k = sort_key(dt, x, i);
+      if (op == 1) k = (dt != kDtI64 && k == top) ? top : (~k & top);  // the smallest first, a NaN still ahead of all
+      if (i == 0 || k > bk) best = i, bk = k;
+    }
+    *out = best;
+    return 0;
+  }
+  int take(uint32_t dt, const void* x, int64_t n, const void* idx, int64_t m, void* y, int64_t* out, void*) override {
+    note("take");
+    const uint64_t es = sort_elem_size(dt, true);
+    if (!es || n < 0 || m < 0) return kBadArgument;
+    int64_t bad = 0;
+    for (int64_t i = 0; i < m; ++i) {
+      const int64_t j = at<int64_t>(idx, i);
+      if (j >= -n && j < n) {
+        memcpy((char*)y + (uint64_t)i * es, (const char*)x + (uint64_t)(j < 0 ? j + n : j) * es, es);
+      } else {
+        memset((char*)y + (uint64_t)i * es, 0, es);
+        ++bad;
+      }
+    }
+    *out = bad;
+    return 0;
+  }
   const char* last_error() override { return "host device"; }
   void info(int64_t v[5]) override {
     v[0] = 256;

@@ -32,6 +32,7 @@ enum {
   BK_MAX_BINS = 4096,               // bins per bk_histogram call
   BK_MAX_AXIS0_COLUMNS = 1 << 18,   // columns bk_reduce_axis / bk_axis_stat reduce along axis 0
   BK_TAIL_MAX_VECTORS = 1024,       // 16-B vectors of a closing reduction's operand (bk_reduce_axis_tail)
+  BK_MAX_SORT_N = 0x7fffffff,       // elements per bk_sort call (it carries 32-bit indices)
 };
 
 // ---- ticketed scratch workspaces -------------------------------------------------
@@ -40,7 +41,7 @@ enum {
 // one must be initialised once (its tickets, and the tables that are "zero
 // between launches", must read zero -- every launch leaves them so).
 enum BkWorkspace {
-  BK_WS_REDUCE = 0,    // bk_reduce, bk_rand_reduce, bk_compare_count
+  BK_WS_REDUCE = 0,    // bk_reduce, bk_rand_reduce, bk_compare_count, bk_int_reduce, bk_arg_reduce, bk_take
   BK_WS_REDUCE_AXIS,   // bk_reduce_axis
   BK_WS_AXIS_STAT,     // bk_axis_stat
   BK_WS_COMPRESS,      // bk_compress
@@ -258,6 +259,27 @@ BK_API int bk_histogram_max_bins();
 // workspace: BK_WS_HISTOGRAM.
 BK_API int bk_histogram(int dtype, const void* x, int64_t n, const void* edges, int bins, void* counts,
                         void* workspace, hipStream_t stream);
+
+// ---- sorting, arg-reductions and gather (sort.hip) ---------------------------------------------
+// The order is numpy's: floats numerically with -0.0 == +0.0 a tie and every NaN, of either sign, tied last;
+// int64 signed; ties keep index order.
+// the bytes of bk_sort's `ws` (a caller-sized data buffer, as bk_gemm_f32x6's, not a ticketed workspace); 0 for an
+// unknown dtype, n < 0 or n > BK_MAX_SORT_N.  Pure host code.
+BK_API int64_t bk_sort_workspace_bytes(int dtype, int64_t n, int with_index);
+// sorted_out[0:n) = np.sort(x) (the sign of a zero among zeros and a NaN's payload aside), index_out[0:n) (int64) =
+// np.argsort(x, kind="stable"); either may be null, not both.  dtype kF32, kF64, kBF16 or kI64; x is only read;
+// x, the outputs and ws (16-byte aligned, ws_bytes >= bk_sort_workspace_bytes(dtype, n, index_out != null)) do not
+// overlap.  An LSD radix sort: two launches per byte of the dtype.  n = 0 is kOk with nothing launched.
+BK_API int bk_sort(int dtype, const void* x, int64_t n, void* sorted_out, void* index_out, void* ws, int64_t ws_bytes,
+                   hipStream_t stream);
+// op 0 argmax, 1 argmin: ONE int64 in *out, numpy's answer (the first occurrence; the first NaN if x holds one).
+// dtype kF32, kF64, kBF16 or kI64.  n < 1 is kBadArgument.  workspace: BK_WS_REDUCE.  One launch.
+BK_API int bk_arg_reduce(int op, int dtype, const void* x, int64_t n, void* workspace, void* out, hipStream_t stream);
+// out[i] = x[idx[i]] for m int64 indices, each in [-n, n) (negative: from the end); elements move by size (f32,
+// f64, bf16, bool, i64).  An index outside that range is never dereferenced: its out element gets zero bits and it
+// is counted.  *bad_out: ONE int64, the number of such indices.  workspace: BK_WS_REDUCE.  One launch (m = 0 too).
+BK_API int bk_take(int dtype, const void* x, int64_t n, const void* idx, int64_t m, void* out, void* workspace,
+                   void* bad_out, hipStream_t stream);
 
 // ---- a matrix against a vector, per-axis statistics (axis.hip) ------------------------------------
 // y[rows x cols] (row stride ldy) = a[rows x cols] (row stride lda) OP v, with

@@ -417,6 +417,7 @@ BK_API int bk_preload(hipStream_t stream) {
       if (rc == kOk && x != kOk) rc = x;
     if (rc == kOk) rc = bk_transpose_bf16(a, b, 64, 64, 64, 64, stream);
     if (rc == kOk) rc = bk_int_binary(0 /*add*/, 1, c, nullptr, 1, c, 64, stream);  // integer.hip
+    if (rc == kOk) rc = bk_arg_reduce(0 /*argmax*/, 0 /*f32*/, c, 64, ws, scalar, stream);  // sort.hip
     const int s = bk_sync(stream);
     if (rc == kOk) rc = s;
   }

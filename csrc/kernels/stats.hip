@@ -9,7 +9,7 @@
 //
 // The LDS counts are u32 atomics.  A wave whose lanes all hit one counter
 // (all-equal data; the top byte of uniform [0, 1) doubles) would serialise on
-// that address, so lds_count first peels the wave's most common indices:
+// that address, so lds_count (bk_keys.hpp) first peels the wave's most common indices:
 // the lanes that share the first active lane's index add their number once
 // (__ballot + popcount), twice over, and only what is left adds lane by lane.
 //
@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "bk_common.hpp"
+#include "bk_keys.hpp"
 #include "bk_ticket.hpp"
 
 namespace bk {
@@ -25,31 +26,12 @@ namespace stats {
 constexpr int kBlock = 256;
 constexpr int kUnroll = 4;          // 16-B loads in flight per lane
 constexpr int kMaxBlocks = 1024;    // 4 per CU; every block merges its counts into the table once
-constexpr int kPeel = 2;            // wave-combined indices before the per-lane atomics
 
 constexpr int kMaxRanks = BK_MAX_RANKS;
 constexpr int kDigitBits = 8;
 constexpr int kDigits = 1 << kDigitBits;
 
 constexpr int kMaxBins = BK_MAX_BINS;
-
-// hist[idx] += 1 for every lane with `on` set; idx is in bounds for those lanes
-__device__ __forceinline__ void lds_count(unsigned* hist, unsigned idx, bool on) {
-  const int lane = threadIdx.x & (kWave - 1);
-  unsigned long long todo = __ballot(on);
-#pragma unroll
-  for (int it = 0; it < kPeel; ++it) {
-    if (todo == 0ull) return;  // (wave-uniform: a ballot)
-    const int leader = __ffsll((long long)todo) - 1;
-    const unsigned lead = (unsigned)__builtin_amdgcn_readlane((int)idx, leader);  // (leader: wave-uniform)
-    const bool same = on && idx == lead;
-    const unsigned long long peers = __ballot(same);
-    if (lane == leader) atomicAdd(&hist[lead], (unsigned)__popcll(peers));
-    todo &= ~peers;
-    on = on && !same;
-  }
-  if (on) atomicAdd(&hist[idx], 1u);
-}
 
 // Calls f(element bits) for every element of x[0:n), all lanes of a block
 // walking the same whole chunks (kUnroll x kBlock vectors: the block's tile).
@@ -102,25 +84,7 @@ inline int64_t head_elements(const void* x, int64_t n) {
 }
 
 // ---- keys ---------------------------------------------------------------------------
-// The order-preserving key of a float's bits (K: the unsigned integer of the
-// dtype's size): negative values flipped whole, the others with the sign bit
-// set, so unsigned key order is numeric order; every NaN, of either sign, maps
-// to the largest key (numpy's sort puts NaNs last).  No other value has it.
-template <typename K> struct Bits;
-template <> struct Bits<uint64_t> { static constexpr uint64_t inf = 0x7ff0000000000000ull; };
-template <> struct Bits<uint32_t> { static constexpr uint32_t inf = 0x7f800000u; };
-template <> struct Bits<uint16_t> { static constexpr uint16_t inf = 0x7f80; };
-
-template <typename K> __device__ __forceinline__ K to_key(K u) {
-  constexpr K sign = (K)((K)1 << (8 * sizeof(K) - 1));
-  if ((K)(u & (K)~sign) > Bits<K>::inf) return (K)~(K)0;
-  return (u & sign) ? (K)~u : (K)(u | sign);
-}
-template <typename K> __device__ __forceinline__ K from_key(K k) {
-  constexpr K sign = (K)((K)1 << (8 * sizeof(K) - 1));
-  if (k == (K)~(K)0) return (K)(Bits<K>::inf | (Bits<K>::inf >> 1));  // a quiet NaN
-  return (k & sign) ? (K)(k ^ sign) : (K)~k;
-}
+// (to_key / from_key: bk_keys.hpp)
 __device__ __forceinline__ double bits_to_double(uint64_t b) { return __longlong_as_double((long long)b); }
 __device__ __forceinline__ double bits_to_double(uint32_t b) { return (double)__uint_as_float(b); }
 __device__ __forceinline__ double bits_to_double(uint16_t b) { return (double)bf16_bits_to_float(b); }

@@ -339,6 +339,73 @@ def int_rows():
         emit(kernel=name, n=n, ms=ms, min_ms=mn, max_ms=mx, GBps=n * 8 / ms / 1e6)
 
 
+def sort_rows():
+    """The sort family (csrc/kernels/sort.hip), n = 1e8, medians of 10 with min and max:
+    `python tools/bench_kernels.py sort` (profiles/sort_kernels.jsonl).  bk.sort and bk.argsort of f32, f64 and
+    int64 on uniform, normal, all-equal and dice data, each beside torch.sort of the same data and bk.sum of the
+    same array as the unit (the bytes model: two reads and one write of the keys per pass, so about 3 sums a pass
+    for keys only); bk.argmax beside bk.sum and torch.argmax; bk.take with a random permutation and with a sorted
+    index beside bk_binary add of equal size and torch's x[idx]."""
+    from bee_code_interpreter_fs_amd.ops.array import driver
+
+    bk.init()
+    emit(kernel="device", **bk.device_info())
+    drv = driver()
+    n = 10**8
+    rng = bk.random.default_rng(5)
+
+    def row(kernel, fn, timer="bk", **kw):
+        ms, mn, mx = spread(fn, timer, reps=10, warmup=2)
+        emit(kernel=kernel, n=n, ms=ms, min_ms=mn, max_ms=mx, **kw)
+        return ms
+
+    def make(dtype, dist):
+        if dtype == "int64":
+            if dist == "uniform":
+                return rng.integers(-(1 << 62), 1 << 62, n)
+            if dist == "normal":
+                return (rng.standard_normal(n) * 1e6).astype("int64")
+            return rng.integers(1, 7, n) if dist == "dice" else bk.full(n, 1.0, "float64").astype("int64")
+        if dist == "uniform":
+            x = rng.random(n, dtype=dtype)
+        elif dist == "normal":
+            x = rng.standard_normal(n, dtype=dtype)
+        elif dist == "dice":
+            x = rng.integers(1, 7, n).astype(dtype)
+        else:
+            x = bk.full(n, 1.0, dtype)
+        return x._materialize()
+
+    for dtype in ("float32", "float64", "int64"):
+        passes = 4 if dtype == "float32" else 8
+        for dist in ("uniform", "normal", "all-equal", "dice"):
+            x = make(dtype, dist)
+            tx = bk.to_torch(x) if dtype != "int64" else torch.from_numpy(x.numpy()).cuda()
+            unit = row(f"sum {dtype} {dist}", lambda: bk.sum(x))
+            ms = row(f"sort {dtype} {dist}", lambda: bk.sort(x), passes=passes)
+            emit(kernel=f"sort {dtype} {dist} vs sum", sums=ms / unit, sums_per_pass=ms / unit / passes, model_sums_per_pass=3.0)
+            ms_a = row(f"argsort {dtype} {dist}", lambda: bk.argsort(x), passes=passes)
+            emit(kernel=f"argsort {dtype} {dist} vs sum", sums=ms_a / unit, sums_per_pass=ms_a / unit / passes)
+            ms_t = row(f"torch.sort {dtype} {dist}", lambda: torch.sort(tx), timer="torch")
+            emit(kernel=f"sort {dtype} {dist} vs torch.sort", ratio=ms / ms_t, argsort_ratio=ms_a / ms_t)
+            if dist == "normal":
+                ms = row(f"argmax {dtype} (incl. 8B readback)", lambda: bk.argmax(x))
+                ms_t = row(f"torch.argmax {dtype} (incl. readback)", lambda: int(torch.argmax(tx)), timer="torch")
+                emit(kernel=f"argmax {dtype} vs sum", ratio=ms / unit, vs_torch=ms / ms_t)
+            del x, tx
+    x = rng.random(n)._materialize()
+    y, z = rng.random(n)._materialize(), bk.empty(n, "float64")
+    tx = bk.to_torch(x)
+    add = row("binary add f64", lambda: drv.binary(0, x.code, 0, x.ptr, y.ptr, 0.0, z.ptr, n))
+    perm = torch.randperm(n, device="cuda")
+    for name, tidx in (("random permutation", perm), ("sorted index", torch.arange(n, device="cuda"))):
+        idx = bk.asarray(tidx.cpu().numpy(), dtype="int64")
+        ms = row(f"take f64, {name} (incl. 8B readback)", lambda: bk.take(x, idx))
+        ms_t = row(f"torch x[idx] f64, {name}", lambda: tx[tidx], timer="torch")
+        emit(kernel=f"take f64, {name} vs binary add", ratio=ms / add, vs_torch=ms / ms_t)
+        del idx
+
+
 def emit(**kw):
     print(json.dumps(kw), flush=True)
 
@@ -424,5 +491,5 @@ def main():
 
 
 if __name__ == "__main__":
-    modes = {"masks": mask_rows, "stats": stats_rows, "axis": axis_rows, "dist": dist_rows, "int": int_rows}
+    modes = {"masks": mask_rows, "stats": stats_rows, "axis": axis_rows, "dist": dist_rows, "int": int_rows, "sort": sort_rows}
     modes[sys.argv[1]]() if len(sys.argv) == 2 and sys.argv[1] in modes else main()
